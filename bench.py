@@ -1,6 +1,6 @@
 """bench.py - mel-frames/sec of one full CompTransTTS train step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 N > 1 without a launcher: bench.py starts the N ranks itself (one process per GPU, like the reference's
 `mp.spawn(train, nprocs=num_gpus)`, train.py:251-252).  Under `python -m torch.distributed.run --nproc-per-node N ... bench.py
@@ -13,12 +13,17 @@ B=16, src<=128, mel<=1024, 11,992 valid frames) resident in HBM.
   --scaling weak   (default): every rank runs its own canonical batch of 16 (what the reference de facto does)
   --scaling strong : ONE global canonical batch of 16 dealt out over the ranks: --shard snake (default, length-balanced) or
                      --shard strided (r, r+N, ...: DistributedSampler, train.py:44 - 28 % more frames on rank 0 than on rank 7 at N = 8)
-value = valid mel frames of all ranks per step / max-over-ranks wall time per step.
+value = valid mel frames of all ranks per step / max-over-ranks wall time per step; ms_per_step = that wall time in milliseconds.
 
-Adds `roofline` (dominant kernel: the implicit-GEMM Conv1d k=9 of the decoder FFN, fp32 MFMA peak 157.3 TFLOP/s), `cpu_baseline`
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR also writes what the last timed step handed
+its caller (loss terms, updated parameters, their gradients) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared.
+
+--full adds `roofline` (dominant kernel: the implicit-GEMM Conv1d k=9 of the decoder FFN, fp32 MFMA peak 157.3 TFLOP/s), `cpu_baseline`
 (oracle restatement of the reference's CPU PyTorch path timed on this host on a bounded sample: C2 = the same B=16 batch, and C1 =
 B=4, at n = physical cores and n = 8 threads) and `pcie_inclusive` (the same step fed by the host data path: collate layout ->
-one pinned buffer -> one async H2D per step -> one D2D refresh of the graph inputs) to the JSON line.
+one pinned buffer -> one async H2D per step -> one D2D refresh of the graph inputs) to the JSON line, and at N = 1 the `secondary`
+configurations, forward-only and mel front-end lines; at N > 1 the per-bucket communication timing.  Each --no-* switch drops one of
+these from a --full run.
 
 Other BASELINE configurations: --block conformer (configs[2]); --dataset VCTK (per-GPU slice of configs[3]); --learn-alignment /
 --prosody liu2021 (together: configs[4] = SURVEY C5).  --no-graph launches eagerly; --no-overlap uses one blocking all-reduce.
@@ -46,6 +51,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: PCIe-inclusive loop, roofline, secondary configurations, CPU baseline, "
+                         "DP communication timing (each can be dropped with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss terms, updated parameters, gradients) as DIR/<name>.npy")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: 16 utterances per GPU; strong: 16 utterances in total, sharded r::N")
     ap.add_argument("--shard", default="strided", choices=["snake", "strided"],
@@ -677,6 +687,36 @@ def measure_secondary(dev, steps=10, warmup=3):
     return out
 
 
+DUMP_SAMPLE = 1 << 22          # elements kept of each flat vector (16 MB in float32): parameters + gradients + losses stay under 64 MB
+
+
+def dump_outputs(step, out_dir, sample=DUMP_SAMPLE):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy.
+    loss_terms  float64: the reference's 9-tuple flattened (dict terms in their order, absent terms NaN)
+    params      float32: every trainable parameter after the optimizer update, flattened in model order
+    grads       float32: the gradients of the same parameters (the arena the step's backward wrote)
+    Vectors longer than `sample` keep a fixed seeded sample of positions (the same positions in both, the same in every run)."""
+    import numpy as np
+    terms = []
+    for t in step.loss_terms:
+        for v in (t.values() if isinstance(t, dict) else [t]):
+            terms.append(float(v.detach().double().reshape(-1)[0]) if torch.is_tensor(v) else (float("nan") if v is None else float(v)))
+    params = torch.cat([p.detach().reshape(-1) for p in step.params])
+    grads = torch.cat([p.grad.detach().reshape(-1) for p in step.params])
+    n = params.numel()
+    if n > sample:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, n, (sample,), generator=g).sort().values
+        d = idx.to(params.device)
+        params, grads = params[d], grads[d]
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"loss_terms": np.asarray(terms, dtype=np.float64), "params": params.float().cpu().numpy(),
+           "grads": grads.float().cpu().numpy()}
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sorted(out)
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -746,6 +786,8 @@ def main():
     elapsed = timed(run_step, a.steps)
     loss_final = float(step.loss_val)
     step.check_kernels()              # stream-K hand-off error words of every workspace (outside the timed region): raises on a failed launch
+    if a.dump_outputs and rank == 0:  # before anything below steps the model again
+        dump_outputs(step, a.dump_outputs)
     if trace is not None and rank == 0:
         for i, t in enumerate(trace):
             print(f"[bench] step {i}: " + " ".join(f"{float(v):.4g}" for v in t), file=sys.stderr)
@@ -760,7 +802,7 @@ def main():
 
     # second loop, PCIe inclusive: a prefetch thread packs + uploads one batch per step; the step starts with ONE D2D refresh
     pcie = None
-    if not a.no_pcie:
+    if a.full and not a.no_pcie:
         n_feed = a.steps + 2
         pf = Prefetcher((collated for _ in range(n_feed)), dev, depth=2)
 
@@ -778,7 +820,7 @@ def main():
 
     # world > 1: a few extra steps with per-bucket timing events (outside the timed region) so that a SCALE run explains itself
     comm = None
-    if world > 1 and step.g_all is None and step.reducer.active:
+    if a.full and world > 1 and step.g_all is None and step.reducer.active:
         step.reducer.start_timing()
         for _ in range(min(5, a.steps)):
             step()
@@ -787,11 +829,11 @@ def main():
         headline = (a.batch == "canonical" and a.block == "transformer_fs2" and a.prosody == "none" and not a.learn_alignment
                     and a.dataset == "LJSpeech")
         roof = (measure_dominant_kernel(dev, make_batch(None, seed=1234), live_traffic=(not a.no_live_traffic and world == 1))
-                if (headline and not a.no_roofline) else None)
+                if (headline and a.full and not a.no_roofline) else None)
         # whole-step roofline view: 157.4 (fs2) / 113.9 (conformer) MFLOP per valid frame vs the fp32 MFMA peak
         step_tflops = (value / world) * (157.4e6 if a.block == "transformer_fs2" else 113.9e6) / 1e12
         secondary = ((measure_secondary(dev) + measure_forward(dev) + measure_mel_frontend(dev))
-                     if (headline and world == 1 and not a.no_secondary) else None)
+                     if (headline and world == 1 and a.full and not a.no_secondary) else None)
         # flat copy of the secondary results (scalars inside `config` survive the driver's record; the full entries stay under `secondary`)
         flat = {}
         for e in secondary or []:
@@ -806,7 +848,7 @@ def main():
                 fr = e.get("step_frac_of_fp32_mfma_peak", e.get("forward_frac_of_fp32_mfma_peak"))
                 if fr is not None:
                     flat[f"sec_{e['key']}_frac"] = round(fr, 4)
-        cpu = None if (a.no_cpu_baseline or world > 1) else cpu_baseline(a.cpu_baseline)      # reported baseline: rank 0 at N = 1 only
+        cpu = None if (not a.full or a.no_cpu_baseline or world > 1) else cpu_baseline(a.cpu_baseline)      # reported baseline: rank 0 at N = 1 only
         nb = len(batch_cpu["src_lens"])
         what = ("supervised durations, multi-speaker (per-GPU slice of BASELINE configs[3] = 64 utterances over 8 GPUs)"
                 if (a.dataset == "VCTK" and not a.learn_alignment and a.prosody == "none") else

@@ -43,7 +43,9 @@ def _worker(rank, world, port, q):
     # rank 1 does not use the last layer -> its gradient there is all zeros on that rank
     _loss(m, X[idx], Y[idx], use_last=(rank == 0)).backward()
     arena.all_reduce_mean()
-    q.put((rank, torch.cat([p.grad.flatten() for p in arena.params])))      # the arena's per-tensor views, alignment gaps dropped
+    # the arena's per-tensor views, alignment gaps dropped; sent as numpy (pickled by value: a tensor would travel as a shared-memory
+    # handle that the parent can only open while this process is still alive)
+    q.put((rank, torch.cat([p.grad.flatten() for p in arena.params]).numpy()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -56,7 +58,7 @@ def test_two_rank_gradient_equals_single_process_average():
     procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
-    res = dict(q.get(timeout=120) for _ in range(world))
+    res = {r: torch.from_numpy(g) for r, g in (q.get(timeout=120) for _ in range(world))}
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -146,7 +148,7 @@ def _real_worker(rank, world, port, q):
     for s in range(len(cuts) + 1):     # backward order: stage 0 first
         red.launch(s)
     red.finish()
-    probe = {n: p.grad.flatten()[:5].clone() for n, p in zip(arena.names, arena.params)
+    probe = {n: p.grad.flatten()[:5].numpy().copy() for n, p in zip(arena.names, arena.params)
              if n in ("postnet.convolutions.4.0.conv.weight", "decoder.layers.3.op.ffn.ffn_1.weight", "decoder.pos_embed_alpha",
                       "encoder.embed_tokens.weight", "variance_adaptor.energy_predictor.linear.weight")}
     q.put((rank, float(arena.flat.double().sum()), probe, red.bucket_bytes()))
@@ -166,6 +168,7 @@ def test_real_model_bucketed_allreduce(world):
     res = {}
     for _ in range(world):
         r, tot, probe, bb = q.get(timeout=300)
+        probe = {n: torch.from_numpy(v) for n, v in probe.items()}
         res[r] = (tot, probe, bb)
     for p in procs:
         p.join(timeout=60)

@@ -166,7 +166,7 @@ def test_bench_gpus_2_spawns_two_ranks_itself(scaling):
     """`python bench.py --gpus 2` with NO launcher: bench.py starts both ranks (the reference's mp.spawn, train.py:251-252), the step is
     4 stage graphs + bucketed all-reduce between the replays + the optimizer graph, rank 0 prints one line with n_gpus 2.  Both ranks
     share this GPU and gloo stands in for RCCL (test hooks CTTS_BENCH_SAME_DEVICE / CTTS_BENCH_BACKEND)."""
-    d = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--batch", "c1", "--scaling", scaling],
+    d = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--batch", "c1", "--scaling", scaling],
                {"CTTS_BENCH_SAME_DEVICE": "1", "CTTS_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["scaling"] == scaling and d["value"] > 0
     assert d["config"]["parallelism"] == "dp2" and np.isfinite(d["config"]["final_loss"])
@@ -204,7 +204,7 @@ def test_bench_rejects_gpus_world_mismatch():
 
 
 def test_single_gpu_bench_line_has_roofline_and_pcie_rates():
-    d = _bench(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-live-traffic"], {})
+    d = _bench(["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-live-traffic"], {})
     assert d["n_gpus"] == 1 and d["roofline"]["frac"] > 0.3 and d["roofline"]["bound"] == "mfma"
     assert d["pcie_inclusive"]["value"] > 0.8 * d["value"]                  # one 8 MB H2D per step hides behind the previous step
     # round 6: what the driver's record keeps are scalars - the three FFN-conv launches flat inside `roofline`, every secondary result flat
@@ -218,6 +218,22 @@ def test_single_gpu_bench_line_has_roofline_and_pcie_rates():
     assert not [k for k in c if k.startswith("sec_error")]
     too_long = [k for blk in (c, r, d["cpu_baseline"] or {}) for k, v in blk.items() if isinstance(v, str) and len(v) > 128]
     assert not too_long, too_long
+
+
+def test_plain_bench_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """a plain run (no --full) times exactly --steps steps and measures nothing else; --dump-outputs writes the last timed step's loss
+    terms, updated parameters and gradients as float arrays within 64 MB"""
+    d = _bench(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], {})
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 / d["config"]["valid_frames_per_gpu"] - 1.0) < 1e-9
+    assert d["roofline"] is None and d["pcie_inclusive"] is None and d["secondary"] is None and d["cpu_baseline"] is None
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["grads.npy", "loss_terms.npy", "params.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 * 2 ** 20
+    out = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert out["loss_terms"].dtype == np.float64 and out["params"].dtype == out["grads"].dtype == np.float32
+    assert out["params"].shape == out["grads"].shape and np.isfinite(out["params"]).all() and np.isfinite(out["grads"]).all()
+    assert out["loss_terms"][0] == np.float32(d["config"]["final_loss"]) and np.abs(out["grads"]).max() > 0
 
 
 def test_rccl_one_rank_group_runs_the_collective_path_on_this_gpu():

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-b() { timeout 300 python $ROOT/bench.py "$@" 2>>$OUT/${R}_bench.err; }
+b() { timeout 300 python $ROOT/bench.py --full "$@" 2>>$OUT/${R}_bench.err; }
 b --steps 20 --warmup 5 > $OUT/${R}_bench_fs2.json
 b --block conformer --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${R}_bench_conformer.json
 b --learn-alignment --steps 10 --warmup 3 --no-cpu-baseline --no-pcie > $OUT/${R}_bench_unsup.json

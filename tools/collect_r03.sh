@@ -6,7 +6,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 # headline + secondary configs (driver-style invocation)
-timeout 900 python $ROOT/bench.py > $OUT/${R}_bench_fs2.json 2> $OUT/${R}_bench.err
+timeout 900 python $ROOT/bench.py --full > $OUT/${R}_bench_fs2.json 2> $OUT/${R}_bench.err
 # eager kernel traces
 for cfg in "fs2:" "conformer:--block conformer"; do
   n=${cfg%%:*}; a=${cfg#*:}; rm -rf /tmp/prof_$n

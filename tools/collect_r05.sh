@@ -6,7 +6,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 # headline + secondary configs (driver-style invocation)
-timeout 900 python $ROOT/bench.py > $OUT/${R}_bench_fs2.json 2> $OUT/${R}_bench.err
+timeout 900 python $ROOT/bench.py --full > $OUT/${R}_bench_fs2.json 2> $OUT/${R}_bench.err
 # the replayed graph: idle time between kernels and per-kernel totals of one step
 for cfg in "fs2:" "conformer:--block conformer" "c5:--prosody liu2021 --learn-alignment"; do
   n=${cfg%%:*}; a=${cfg#*:}
