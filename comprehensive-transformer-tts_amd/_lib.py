@@ -48,6 +48,22 @@ class GemmDesc(C.Structure):
     ]
 
 
+class VconvDesc(C.Structure):
+    """ctts_vconv_desc of include/ctts.h (ctypes zero-initialises it)"""
+    _fields_ = [
+        ("x", _vp), ("sxb", _i64), ("sxt", _i64), ("sxc", _i64),
+        ("B", _i32), ("T", _i32), ("Cin", _i32), ("Cout", _i32), ("k", _i32), ("dil", _i32),
+        ("transposed_u", _i32),
+        ("act_in", _i32), ("slope", _f32),
+        ("w", _vp), ("w_planes", _vp),
+        ("bias", _vp),
+        ("R", _vp),
+        ("out", _vp),
+        ("alpha", _f32), ("beta", _f32),
+        ("bf16_split", _i32),
+    ]
+
+
 class PsumTask(C.Structure):
     """ctts_psum_task of include/ctts.h"""
     _fields_ = [("src", _vp), ("dst", _vp), ("n", _i64), ("stride", _i64), ("count", _i32), ("alpha", _f32)]
@@ -142,6 +158,8 @@ _SIGNATURES = {
     "ctts_gru_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "ctts_softmax_rect_fwd": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp],
     "ctts_softmax_rect_bwd": [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp],
+    "ctts_vocoder_conv": [C.POINTER(VconvDesc), _vp],
+    "ctts_vocoder_post": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _f32, _vp, _vp],
     "ctts_comm_unique_id": [_vp],
     "ctts_comm_create": [C.POINTER(_vp), _i32, _i32, _vp],
     "ctts_comm_destroy": [_vp],

@@ -1229,3 +1229,79 @@ def mel_spectrogram_fft(y, window, ws, n_fft, hop, n_mel, clip=1e-5, want_mag=Fa
                                         None if range_flag is None else range_flag.data_ptr(),      # device or pinned host memory
                                         _stream()), "ctts_mel_spectrogram")
     return mel, energy, mag
+
+
+# ---- HiFi-GAN vocoder (csrc/vocoder.hip) ------------------------------------------------------------------------------------
+def vocoder_pack_weight(weight, transposed_u=0, planes=None):
+    """Folded Conv1d weight [Cout, Cin, k] (transposed_u = 0) or ConvTranspose1d weight [Cin, Cout, k] (transposed_u = u) -> the packed
+    operand of ctts_vocoder_conv: (w [roundup(N, 128), taps * roundup(Cin, 32)] fp32, w_planes or None).  `planes`: also split it
+    (ctts_split_planes; None = the module default BF16_SPLIT).  Weight packing is a one-time layout change of a constant."""
+    w = weight.detach().float()
+    if transposed_u:
+        cin, cout, k = w.shape
+        u = int(transposed_u)
+        J = k // u
+        # [Cin, Cout, J, u] (tap index r + j u) -> [u, Cout, J, Cin], taps reversed (tap' = J - 1 - j): column r Cout + co
+        g = w.reshape(cin, cout, J, u).permute(3, 1, 2, 0).flip(2).reshape(u * cout, J, cin)
+    else:
+        g = w.permute(0, 2, 1)                         # [Cout, k, Cin]
+    N, taps, cin = g.shape
+    npad, cpad = -(-N // 128) * 128, -(-cin // 32) * 32
+    packed = torch.zeros(npad, taps, cpad, dtype=torch.float32, device=w.device)
+    packed[:N, :, :cin] = g
+    packed = packed.reshape(npad, taps * cpad)
+    use = BF16_SPLIT if planes is None else planes
+    return packed, (split_planes([packed])[0] if use else None)
+
+
+def vocoder_conv(x, w, w_planes, Cin, Cout, k, dil=1, transposed_u=0, slope=None, bias=None, R=None, out=None, alpha=1.0, beta=0.0,
+                 bf16_split=None):
+    """One generator layer (include/ctts.h ctts_vocoder_conv).  x: [B, T, Cin] with any strides (fp32); w / w_planes from
+    vocoder_pack_weight; slope: leaky_relu slope applied to x on load, or None.  -> out [B, T_out, Cout] (T_out = T or T u):
+    out = beta * out + alpha * (conv + bias + R)."""
+    if x.dtype != torch.float32 or x.dim() != 3:
+        raise _lib.CttsError(f"vocoder_conv: x must be a 3-D float32 tensor [B, T, Cin], got {x.dtype} {tuple(x.shape)}")
+    B, T, cin = x.shape
+    if cin != Cin:
+        raise _lib.CttsError(f"vocoder_conv: x has {cin} channels, the layer {Cin}")
+    Tout = T * transposed_u if transposed_u else T
+    split = BF16_SPLIT if bf16_split is None else int(bf16_split)
+    if out is None:
+        if beta != 0.0:
+            raise _lib.CttsError("vocoder_conv: beta != 0 needs `out`")
+        out = torch.empty(B, Tout, Cout, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, Tout, Cout):
+        raise _lib.CttsError(f"vocoder_conv: out has shape {tuple(out.shape)}, expected {(B, Tout, Cout)}")
+    if split and w_planes is None:
+        raise _lib.CttsError("vocoder_conv: the split arithmetic needs w_planes")
+    N, taps = (transposed_u * Cout, k // transposed_u) if transposed_u else (Cout, k)
+    wshape = (-(-N // 128) * 128, taps * (-(-Cin // 32) * 32))
+    if tuple(w.shape) != wshape or (split and w_planes.numel() != 3 * w.numel()):
+        raise _lib.CttsError(f"vocoder_conv: packed weight {tuple(w.shape)} does not match the layer (expected {wshape})")
+    d = _lib.VconvDesc()
+    d.x = _p(x)
+    d.sxb, d.sxt, d.sxc = (int(s) for s in x.stride())
+    d.B, d.T, d.Cin, d.Cout, d.k, d.dil = B, T, int(Cin), int(Cout), int(k), int(dil)
+    d.transposed_u = int(transposed_u)
+    d.act_in = 0 if slope is None else 1
+    d.slope = 0.0 if slope is None else float(slope)
+    d.w = _p(_f32c(w, "vocoder weight"))
+    d.w_planes = None if (w_planes is None or not split) else _p(w_planes)
+    d.bias = _p(None if bias is None else _f32c(bias, "bias"))
+    d.R = _p(None if R is None else _f32c(R, "R"))
+    d.out = _p(_f32c(out, "out"))
+    d.alpha, d.beta = float(alpha), float(beta)
+    d.bf16_split = split
+    _lib.check(_lib.load().ctts_vocoder_conv(C.byref(d), _stream()), "ctts_vocoder_conv")
+    return out
+
+
+def vocoder_post(x, w, bias, slope=0.01, out=None):
+    """conv_post + tanh (include/ctts.h ctts_vocoder_post): x [B, T, C] dense, w [k, C] (= weight[0].T), bias [1] -> [B, 1, T]."""
+    B, T, Cc = x.shape
+    k = w.shape[0]
+    if out is None:
+        out = torch.empty(B, 1, T, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().ctts_vocoder_post(_p(_f32c(x, "x")), B, T, Cc, int(k), _p(_f32c(w, "w")), _p(_f32c(bias, "bias")), float(slope),
+                                             _p(_f32c(out, "out")), _stream()), "ctts_vocoder_post")
+    return out

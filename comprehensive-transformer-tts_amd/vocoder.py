@@ -1,0 +1,187 @@
+"""HiFi-GAN generator, inference only, on the gfx950 kernels of csrc/vocoder.hip (include/ctts.h ctts_vocoder_conv / ctts_vocoder_post).
+
+Replaces the reference's `hifigan.Generator` (hifigan/models.py:112-173) where `utils/model.py:42-92` (`get_vocoder`, `vocoder_infer`)
+builds and runs it: same constructor (`Generator(h)`, `h` the AttrDict of hifigan/config.json), same module tree and state-dict keys in
+both weight forms (weight norm: `*.weight_g` / `*.weight_v` / `*.bias`; after `remove_weight_norm()`: `*.weight` / `*.bias`), so a
+released checkpoint's `ckpt["generator"]` loads unchanged.  Like the reference (models.py:121) it always builds type-1 ResBlocks.
+
+`forward(mel [B, 80, T]) -> wav [B, 1, 256 T]` on device tensors only (a CPU tensor raises: there is no CPU path), no autograd graph.
+The mel may be the transposed view of the acoustic model's channel-last [B, T, 80] output: the first layer reads it through its strides,
+no copy.  Per forward: 1 + num_upsamples + 6 x num_upsamples x num_kernels + 1 launches (78 for V1), every leaky_relu, residual add,
+`xs += resblock(x)` and `/ num_kernels` fused into a convolution's load or epilogue.  Arithmetic: kernels.BF16_SPLIT (CTTS_X6=0 = exact
+fp32 MFMA; default = the exact three-way bf16 split).  The folded, packed (and split) weights are cached and rebuilt when a parameter
+changes (load_state_dict, remove_weight_norm, .to(), in-place edits: version counters + kernels.WEIGHTS_EPOCH)."""
+import torch
+import torch.nn as nn
+from torch.nn import Conv1d, ConvTranspose1d
+from torch.nn.utils import remove_weight_norm as _remove_weight_norm
+
+from . import _lib
+from . import kernels as K
+
+LRELU_SLOPE = 0.1          # models.py:7
+POST_SLOPE = 0.01          # F.leaky_relu's default, models.py:161
+
+
+class AttrDict(dict):
+    """hifigan/__init__.py's config container: keys readable as attributes."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.__dict__ = self
+
+
+def get_padding(kernel_size, dilation=1):
+    return int((kernel_size * dilation - dilation) / 2)
+
+
+def _weight_norm(m):
+    # the reference's torch.nn.utils.weight_norm (dim 0: output channels of a Conv1d, INPUT channels of a ConvTranspose1d), whose
+    # parameter names a checkpoint carries; its forward pre-hook never runs here (the kernels fold g / v themselves)
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", FutureWarning)
+        return torch.nn.utils.weight_norm(m)
+
+
+def _folded_weight(m):
+    """effective weight of a (possibly weight-normed) conv: g v / ||v|| over every dim but 0, as WeightNorm.compute_weight"""
+    if hasattr(m, "weight_g") and hasattr(m, "weight_v"):
+        return torch._weight_norm(m.weight_v, m.weight_g, 0)
+    return m.weight
+
+
+class ResBlock(nn.Module):
+    """models.py:18-109 (ResBlock1): three (dilated conv, conv) pairs with a residual each."""
+
+    def __init__(self, h, channels, kernel_size=3, dilation=(1, 3, 5)):
+        super().__init__()
+        self.h = h
+        self.kernel_size = kernel_size
+        self.dilation = tuple(dilation[:3])
+        self.convs1 = nn.ModuleList([_weight_norm(Conv1d(channels, channels, kernel_size, 1, dilation=d, padding=get_padding(kernel_size, d)))
+                                     for d in self.dilation])
+        self.convs2 = nn.ModuleList([_weight_norm(Conv1d(channels, channels, kernel_size, 1, dilation=1, padding=get_padding(kernel_size, 1)))
+                                     for _ in self.dilation])
+
+    def remove_weight_norm(self):
+        for m in self.convs1:
+            _remove_weight_norm(m)
+        for m in self.convs2:
+            _remove_weight_norm(m)
+
+
+class Generator(nn.Module):
+    """models.py:112-173 on the HIP kernels.  Raises NotImplementedError for an upsampler the polyphase kernel does not cover
+    (kernel % rate != 0 or kernel - rate odd) or a dilated conv whose halo exceeds 64 rows."""
+
+    def __init__(self, h):
+        super().__init__()
+        self.h = h
+        self.num_kernels = len(h.resblock_kernel_sizes)
+        self.num_upsamples = len(h.upsample_rates)
+        for u, k in zip(h.upsample_rates, h.upsample_kernel_sizes):
+            if k % u or (k - u) % 2:
+                raise NotImplementedError(f"HiFi-GAN upsampler with rate {u} and kernel {k}: the native ConvTranspose1d needs "
+                                          "kernel % rate == 0 and (kernel - rate) even")
+            if k // u - 1 > 64:
+                raise NotImplementedError(f"HiFi-GAN upsampler kernel {k} / rate {u}: more than 65 taps")
+        for k, ds in zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes):
+            if k % 2 == 0 or any((k - 1) * d > 64 for d in ds[:3]) or len(ds) < 3:
+                raise NotImplementedError(f"HiFi-GAN ResBlock kernel {k} dilations {ds}: the native conv needs an odd kernel, three "
+                                          "dilations and (kernel - 1) x dilation <= 64")
+        c0 = h.upsample_initial_channel
+        self.conv_pre = _weight_norm(Conv1d(80, c0, 7, 1, padding=3))
+        self.ups = nn.ModuleList()
+        for i, (u, k) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
+            self.ups.append(_weight_norm(ConvTranspose1d(c0 // (2 ** i), c0 // (2 ** (i + 1)), k, u, padding=(k - u) // 2)))
+        self.resblocks = nn.ModuleList()
+        ch = c0
+        for i in range(len(self.ups)):
+            ch = c0 // (2 ** (i + 1))
+            for k, d in zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes):
+                self.resblocks.append(ResBlock(h, ch, k, d))
+        self.conv_post = _weight_norm(Conv1d(ch, 1, 7, 1, padding=3))
+        self._cache_key = None
+        self._cache = None
+
+    def remove_weight_norm(self):
+        for m in self.ups:
+            _remove_weight_norm(m)
+        for m in self.resblocks:
+            m.remove_weight_norm()
+        _remove_weight_norm(self.conv_pre)
+        _remove_weight_norm(self.conv_post)
+
+    # ---- packed weights ----------------------------------------------------------------------------------------------------------
+    def _key(self, split):
+        return (split, K.WEIGHTS_EPOCH[0], tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in self.parameters()))
+
+    def _packed(self, split):
+        key = self._key(split)
+        if key == self._cache_key:
+            return self._cache
+
+        def conv(m, u=0):
+            w, wp = K.vocoder_pack_weight(_folded_weight(m), transposed_u=u, planes=split)
+            return (w, wp, m.bias.detach().float().contiguous())
+
+        with torch.no_grad():
+            pre = conv(self.conv_pre)
+            ups = [conv(m, m.stride[0]) for m in self.ups]
+            rbs = [[(conv(c1), conv(c2)) for c1, c2 in zip(rb.convs1, rb.convs2)] for rb in self.resblocks]
+            wpost = _folded_weight(self.conv_post)[0].detach().float().t().contiguous()        # [k, C]
+            post = (wpost, self.conv_post.bias.detach().float().contiguous())
+        self._cache = (pre, ups, rbs, post)
+        self._cache_key = key
+        return self._cache
+
+    # ---- forward -----------------------------------------------------------------------------------------------------------------
+    def forward(self, x):
+        return self._forward(x)
+
+    def _forward(self, x, stage_cb=None):
+        """forward; stage_cb(name) after conv_pre, each upsampling stage and conv_post (tools/bench_vocoder.py's per-stage events)"""
+        if not x.is_cuda:
+            raise _lib.CttsError("hifigan Generator: the mel must be a device (HIP) tensor - there is no CPU path")
+        if x.dim() != 3 or x.shape[1] != 80:
+            raise _lib.CttsError(f"hifigan Generator: expected mel [B, 80, T], got {tuple(x.shape)}")
+        split = K.BF16_SPLIT
+        with torch.no_grad():
+            pre, ups, rbs, post = self._packed(split)
+            xt = x.float().transpose(1, 2)                     # [B, T, 80] channel-last view (the model's own mel layout)
+            c0 = self.h.upsample_initial_channel
+            w, wp, b = pre
+            hcur = K.vocoder_conv(xt, w, wp, 80, c0, 7, 1, bias=b, bf16_split=split)                           # models.py:146
+            if stage_cb:
+                stage_cb("conv_pre")
+            nk = self.num_kernels
+            for i in range(self.num_upsamples):
+                u, kup = self.h.upsample_rates[i], self.h.upsample_kernel_sizes[i]
+                cin, cout = c0 // (2 ** i), c0 // (2 ** (i + 1))
+                w, wp, b = ups[i]
+                hcur = K.vocoder_conv(hcur, w, wp, cin, cout, kup, 1, transposed_u=u, slope=LRELU_SLOPE, bias=b,   # models.py:148-149
+                                      bf16_split=split)
+                xs = torch.empty_like(hcur)
+                for j in range(nk):                                                                            # models.py:150-158
+                    rb = self.resblocks[i * nk + j]
+                    k = rb.kernel_size
+                    cur = hcur
+                    for l, d in enumerate(rb.dilation):                                                         # models.py:96-104
+                        (w1, wp1, b1), (w2, wp2, b2) = rbs[i * nk + j][l]
+                        t = K.vocoder_conv(cur, w1, wp1, cout, cout, k, d, slope=LRELU_SLOPE, bias=b1, bf16_split=split)
+                        if l < len(rb.dilation) - 1:
+                            cur = K.vocoder_conv(t, w2, wp2, cout, cout, k, 1, slope=LRELU_SLOPE, bias=b2, R=cur, bf16_split=split)
+                        else:             # xs = resblock_0(x); xs += resblock_j(x); x = xs / num_kernels - in the epilogue
+                            last = j == nk - 1
+                            K.vocoder_conv(t, w2, wp2, cout, cout, k, 1, slope=LRELU_SLOPE, bias=b2, R=cur, out=xs,
+                                           alpha=1.0 / nk if last else 1.0, beta=0.0 if j == 0 else (1.0 / nk if last else 1.0),
+                                           bf16_split=split)
+                hcur = xs
+                if stage_cb:
+                    stage_cb(f"stage{i}")
+            wpost, bpost = post
+            wav = K.vocoder_post(hcur, wpost, bpost, POST_SLOPE)                                              # models.py:161-163
+            if stage_cb:
+                stage_cb("conv_post")
+            return wav

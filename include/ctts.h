@@ -525,6 +525,44 @@ int ctts_mel_l1_bwd(const float* p1, const float* p2, const float* tgt, const fl
                     float* d2, int64_t rows, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * HiFi-GAN V1 vocoder, inference (csrc/vocoder.hip; comprehensive-transformer-tts_amd/vocoder.py).  Replaces hifigan/models.py:112-173
+ * `Generator.forward` as called by utils/model.py:74-92 `vocoder_infer` (synthesize.py:196, utils/tools.py:206-350).
+ * ctts_vocoder_conv: one Conv1d of the generator per launch, implicit GEMM on the MFMA, input tile + halo staged once per 32 channels.
+ *   transposed_u == 0: Conv1d(Cin, Cout, k, stride 1, dilation dil, padding dil (k - 1) / 2), k odd  - conv_pre (models.py:117),
+ *     ResBlock convs1 / convs2 (models.py:24-86); T_out = T.
+ *   transposed_u == u >= 1: ConvTranspose1d(Cin, Cout, k, stride u, padding (k - u) / 2), k % u == 0, (k - u) even - ups (models.py:
+ *     121-131), run as the polyphase k/u-tap GEMM with N = u Cout; T_out = T u.
+ *   x: element (b, t, c) at x[b sxb + t sxt + c sxc] (any strides: the mel's [B, 80, T] view of a [B, T, 80] tensor is sxc = 1);
+ *   act_in = 1 applies leaky_relu(., slope) to x on load (models.py:98,100,150).
+ *   w: packed weight [roundup(N, 128)][taps][roundup(Cin, 32)] fp32, zero padded (N = Cout or u Cout; taps = k or k / u):
+ *     Conv1d          w[co][tap][ci]         = weight[co][ci][tap]
+ *     ConvTranspose1d w[r Cout + co][tap][ci] = weight[ci][co][r + (k / u - 1 - tap) u]
+ *     16-byte aligned.  w_planes: ctts_split_planes of w (ld = taps roundup(Cin, 32)), required when bf16_split != 0.
+ *   out [B, T_out, Cout] dense: out = beta * out + alpha * (conv + bias[co] + R[b, t, co]); bias / R may be NULL; beta == 0 never
+ *     reads out.  out must not alias x.
+ *   bf16_split != 0: the exact three-way bf16 split of include/ctts.h's plane kernels (six MFMA terms, fp32 accumulation, products
+ *     within one fp32 rounding); 0: exact fp32 MFMA.  Bit-reproducible (no atomics).
+ * ctts_vocoder_post: out[b, t] = tanh(bias[0] + sum_{tap < k, c} leaky_relu(x[b, t + tap - (k - 1) / 2, c], slope) w[tap][c]),
+ *   x [B, T, C] dense, out [B, 1, T] - conv_post with its leaky_relu (default slope 0.01) and tanh (models.py:161-163); fp32 VALU.
+ * Descriptors must be zero-initialised (fields added later default to 0). */
+typedef struct ctts_vconv_desc {
+  const float* x;
+  int64_t sxb, sxt, sxc;
+  int32_t B, T, Cin, Cout, k, dil;
+  int32_t transposed_u;
+  int32_t act_in; float slope;
+  const float* w; const uint16_t* w_planes;
+  const float* bias;
+  const float* R;
+  float* out;
+  float alpha, beta;
+  int32_t bf16_split;
+} ctts_vconv_desc;
+int ctts_vocoder_conv(const ctts_vconv_desc* d, void* stream);
+int ctts_vocoder_post(const float* x, int B, int T, int C, int k, const float* w, const float* bias, float slope, float* out,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (SURVEY.md section 8(b) `ctts_allreduce_*`, 8(e); replaces what
  * `DistributedDataParallel(model, device_ids=[rank])` does after backward in the reference: train.py:29-35,58,112).
  *   ctts_comm_unique_id  rank 0 draws CTTS_COMM_ID_BYTES opaque bytes (ncclGetUniqueId) and hands them to every rank by any side
