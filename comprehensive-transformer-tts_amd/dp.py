@@ -112,7 +112,10 @@ def stage_plan(model, n_cuts=3):
     decoder input: stage 0 = PostNet + mel_linear + upper decoder layers, ..., last stage = variance adaptor + encoder."""
     dec = model.decoder
     stack_name = "layers" if hasattr(dec, "layers") else "layer_stack"
-    L = len(getattr(dec, stack_name))
+    # fastformer: the layers sit one level deeper (decoder.layer_stack.layers.{i}); its tied logit projections are named under layer 0,
+    # so their bucket closes after the stage that runs layer 0's backward - the last one to add to them
+    nested = not hasattr(getattr(dec, stack_name), "__len__")
+    L = len(getattr(dec, stack_name).layers if nested else getattr(dec, stack_name))
     n_cuts = max(1, min(int(n_cuts), L))
     # layer indices at whose INPUT the forward is severed, descending; the last cut is always the decoder input
     inner = sorted({(L * k) // n_cuts for k in range(1, n_cuts)} - {0}, reverse=True)
@@ -123,7 +126,7 @@ def stage_plan(model, n_cuts=3):
         if name.startswith("postnet.") or name.startswith("mel_linear."):
             return 0
         if name.startswith(f"decoder.{stack_name}."):
-            li = int(name.split(".")[2])
+            li = int(name.split(".")[3 if nested else 2])
             for s, lo in enumerate(bounds):
                 if li >= lo:
                     return s

@@ -1305,3 +1305,83 @@ def vocoder_post(x, w, bias, slope=0.01, out=None):
     _lib.check(_lib.load().ctts_vocoder_post(_p(_f32c(x, "x")), B, T, Cc, int(k), _p(_f32c(w, "w")), _p(_f32c(bias, "bias")), float(slope),
                                              _p(_f32c(out, "out")), _stream()), "ctts_vocoder_post")
     return out
+
+
+# ---- Fastformer additive attention (csrc/fastformer.hip) ----------------------------------------------------------------------
+def _rows_ld(t, C, name):
+    """(row stride) of a [B*T, C]-shaped fp32 operand that may be a column slice of a wider matrix (unit column stride)"""
+    if t.dtype != torch.float32 or t.stride(-1) != 1 or t.dim() < 2:
+        raise _lib.CttsError(f"{name}: need a float32 matrix with unit column stride, got {t.dtype} {tuple(t.shape)} {t.stride()}")
+    ld = t.stride(-2)
+    if t.dim() == 3 and t.stride(0) != ld * t.shape[1]:
+        raise _lib.CttsError(f"{name}: batch stride {t.stride(0)} is not T * row stride")
+    return ld
+
+
+def fastformer_workspace(B, T, H, Cc, device):
+    n = _lib.load().ctts_fastformer_workspace_floats(int(B), int(T), int(H), int(Cc))
+    return torch.empty(max(int(n), 1), dtype=torch.float32, device=device)
+
+
+def fastformer_pool_fwd(s, V, lens, B, T, H, div):
+    """alpha = softmax_t(s / div + (t < lens[b] ? -10000 : 0)) per (b, h);  p[b, c] = sum_t alpha[b, t, c // D] V[b, t, c].
+    s: [B*T, H] logits (row stride may exceed H), V: [B*T, C] values -> (p [B, C], stats [B, H, 2])"""
+    Cc = V.shape[-1]
+    p = torch.empty(B, Cc, dtype=torch.float32, device=V.device)
+    stats = torch.empty(B, H, 2, dtype=torch.float32, device=V.device)
+    ws = fastformer_workspace(B, T, H, Cc, V.device)
+    _lib.check(_lib.load().ctts_fastformer_pool_fwd(_p(s), _rows_ld(s, H, "s"), _p(V), _rows_ld(V, Cc, "V"), _p(lens), _p(p), _p(stats),
+                                                    _p(ws), int(B), int(T), int(H), int(Cc), float(div), _stream()), "ctts_fastformer_pool_fwd")
+    return p, stats
+
+
+def fastformer_pool_bwd(dp, p, stats, s, V, lens, B, T, H, div, dV_in=None):
+    """-> (dV [B*T, C] = dV_in + alpha dp,  ds [B*T, H]); dV is written into dV_in when it is given"""
+    Cc = V.shape[-1]
+    dV = dV_in if dV_in is not None else torch.empty(B * T, Cc, dtype=torch.float32, device=V.device)
+    ds = torch.empty(B * T, H, dtype=torch.float32, device=V.device)
+    _lib.check(_lib.load().ctts_fastformer_pool_bwd(_p(_f32c(dp, "dp")), _p(_f32c(p, "p")), _p(_f32c(stats, "stats")), _p(s),
+                                                    _rows_ld(s, H, "s"), _p(V), _rows_ld(V, Cc, "V"), _p(lens),
+                                                    _p(None if dV_in is None else _f32c(dV_in, "dV_in")), _p(dV), _p(ds), int(B), int(T),
+                                                    int(H), int(Cc), float(div), _stream()), "ctts_fastformer_pool_bwd")
+    return dV, ds
+
+
+def fastformer_bcast(X, p, B, T):
+    """Y [B*T, C] = X[b, t, :] * p[b, :]"""
+    Cc = X.shape[-1]
+    Y = torch.empty(B * T, Cc, dtype=torch.float32, device=X.device)
+    _lib.check(_lib.load().ctts_fastformer_bcast(_p(X), _rows_ld(X, Cc, "X"), _p(_f32c(p, "p")), _p(Y), int(B), int(T), int(Cc), _stream()),
+               "ctts_fastformer_bcast")
+    return Y
+
+
+def fastformer_bcast_bwd(dY1, X, p, B, T, dY2=None, dX_in=None, out=None):
+    """dy = dY1 + dY2 -> (dX = dX_in + dy * p[b],  dp [B, C] = sum_t dy * X); dX goes to `out` (may be dX_in) or a new tensor"""
+    Cc = X.shape[-1]
+    dX = out if out is not None else torch.empty(B * T, Cc, dtype=torch.float32, device=X.device)
+    dp = torch.empty(B, Cc, dtype=torch.float32, device=X.device)
+    ws = fastformer_workspace(B, T, 0, Cc, X.device)
+    _lib.check(_lib.load().ctts_fastformer_bcast_bwd(_p(_f32c(dY1, "dY1")), _p(None if dY2 is None else _f32c(dY2, "dY2")), _p(X),
+                                                     _rows_ld(X, Cc, "X"), _p(_f32c(p, "p")),
+                                                     _p(None if dX_in is None else _f32c(dX_in, "dX_in")), _p(dX), _p(dp), _p(ws), int(B),
+                                                     int(T), int(Cc), _stream()), "ctts_fastformer_bcast_bwd")
+    return dX, dp
+
+
+def fastformer_resdrop(x, t, rowscale=None, p_drop=0.0, seed=None, drop_offset=0):
+    """y = rowscale * (x + dropout(t))"""
+    Cc = t.shape[-1]
+    y = torch.empty_like(t)
+    _lib.check(_lib.load().ctts_fastformer_resdrop(_p(_f32c(x, "x")), _p(_f32c(t, "t")), _p(y), None, t.numel() // Cc, int(Cc), _p(rowscale),
+                                                   float(p_drop), _p(seed), int(drop_offset), 0, _stream()), "ctts_fastformer_resdrop")
+    return y
+
+
+def fastformer_resdrop_bwd(dy, rowscale=None, p_drop=0.0, seed=None, drop_offset=0):
+    """-> (dx = rowscale * dy,  dt = rowscale * dropout(dy))"""
+    Cc = dy.shape[-1]
+    dt, dx = torch.empty_like(dy), torch.empty_like(dy)
+    _lib.check(_lib.load().ctts_fastformer_resdrop(None, _p(_f32c(dy, "dy")), _p(dt), _p(dx), dy.numel() // Cc, int(Cc), _p(rowscale),
+                                                   float(p_drop), _p(seed), int(drop_offset), 1, _stream()), "ctts_fastformer_resdrop")
+    return dx, dt

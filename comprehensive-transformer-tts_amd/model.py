@@ -774,7 +774,9 @@ class CompTransTTS(nn.Module):
             enc_cls, dec_cls = TextEncoder, Decoder
         elif bt == "conformer":
             from .conformer import TextEncoder as enc_cls, Decoder as dec_cls
-        elif bt in ("transformer", "lstransformer", "fastformer", "reformer"):
+        elif bt == "fastformer":
+            from .fastformer import TextEncoder as enc_cls, Decoder as dec_cls
+        elif bt in ("transformer", "lstransformer", "reformer"):
             raise NotImplementedError(f"block_type '{bt}' has no MI355X-native plugin (SURVEY.md section 2 #6: out of scope; the "
                                       "plugin contract is kept, so a third-party TextEncoder/Decoder pair still plugs in)")
         else:
@@ -800,11 +802,15 @@ class CompTransTTS(nn.Module):
     # blocks.py:286-288 ConvNorm; torch defaults for nn.Conv1d / nn.Linear elsewhere)
     def reset_parameters(self):
         params = dict(self.named_parameters())
-        conformer = self.model_config["block_type"] == "conformer"
-        if conformer:
+        conformer = self.model_config["block_type"] in ("conformer", "fastformer")      # stacks with initialisers of their own
+        if self.model_config["block_type"] == "conformer":
             from .conformer import reset_conformer_parameters
             reset_conformer_parameters(self.encoder)
             reset_conformer_parameters(self.decoder)
+        elif self.model_config["block_type"] == "fastformer":
+            from .fastformer import reset_fastformer_parameters
+            reset_fastformer_parameters(self.encoder)
+            reset_fastformer_parameters(self.decoder)
         prosody_mods = [m for n, m in self.variance_adaptor.named_children() if "prosody" in n and not n.endswith("_prj")]
         if prosody_mods:
             from .prosody import reset_prosody_parameters

@@ -1712,3 +1712,120 @@ class _BinLoss(torch.autograd.Function):
 def bin_loss(hard, soft):
     """BinLoss (loss.py:380-386): -sum(log(clamp(soft, 1e-12)) * hard) / sum(hard), deterministic two-stage reduction"""
     return _BinLoss.apply(soft, hard)
+
+
+# ---- Fastformer additive attention (csrc/fastformer.hip; reference fastformer.py FastAttention) ------------------------------------
+def _ff_linear(x, w, b, R=None):
+    M, Kd = x.shape
+    N = w.shape[0]
+    out = torch.empty(M, N, dtype=torch.float32, device=x.device)
+    K.gemm(x, w, out, M, N, Kd, Kd, Kd, N, True, True, bias=b, R=R, ldr=N)
+    return out
+
+
+def _ff_dgrad(dY, w, R=None):
+    """dX = dY w (+ R)"""
+    M, N = dY.shape
+    Kd = w.shape[1]
+    dX = torch.empty(M, Kd, dtype=torch.float32, device=dY.device)
+    K.gemm(dY, w, dX, M, Kd, N, N, Kd, Kd, True, False, R=R, ldr=Kd)
+    return dX
+
+
+def _ff_wgrad(dY, x, w, b, want_w, want_b):
+    """weight / bias gradient of y = x w^T + b; accumulated straight into param.grad under gradient-accumulation fusion (a tied weight
+    then collects every layer's contribution in place), else returned"""
+    M, N = dY.shape
+    Kd = x.shape[1]
+    dW = dB = None
+    if want_w:
+        fused = _fusable(w)
+        dW = _grad_of(w) if fused else torch.empty_like(w)
+        with _wgrad_scope(fused, dY, x, rows=M):
+            K.gemm(dY, x, dW, N, Kd, M, N, Kd, Kd, False, False, split_k=max(2, _split_k_for(N, Kd, M)),
+                   defer=fused and _WGRAD["stream"] is None, split_overwrite=not fused)
+        if fused:
+            dW = None
+    if want_b:
+        if _fusable(b):
+            K.colsum(dY, acc_into=_grad_of(b))
+        else:
+            dB = K.colsum(dY)
+    return dW, dB
+
+
+class _FastAttention(torch.autograd.Function):
+    """T2 = Q + transform(pk * Q) for h = LayerNorm(x) [B, T, C] (fastformer.py FastAttention.forward without its dropout):
+        Q = h Wq^T + bq,  K = h Wk^T + bk,  s_q = Q Wql^T + bql,  pq = pool(s_q, Q),  QK = K * pq,
+        s_k = QK Wkl^T + bkl,  pk = pool(s_k, QK),  WV = pk * Q,  T2 = WV Wt^T + bt + Q
+    pool(s, V)[b, c] = sum_t softmax_t(s / sqrt(D) + mask)[b, t, c // D] V[b, t, c] over the PADDED length (ctts_fastformer_pool_fwd).
+    One autograd node: every tensor with several consumers (Q: four, QK: two, h: two) gets its gradient summed inside the kernels and the
+    GEMM epilogues (dX_in / dV_in / R), so the backward issues no stock-torch add."""
+
+    @staticmethod
+    def forward(ctx, h, lens, n_heads, wq, bq, wk, bk, wql, bql, wkl, bkl, wt, bt):
+        h = h.contiguous()
+        B, T, Cc = h.shape
+        M, H = B * T, int(n_heads)
+        div = float((Cc // H) ** 0.5)
+        hm = h.view(M, Cc)
+        Q = _ff_linear(hm, wq, bq)
+        Kt = _ff_linear(hm, wk, bk)
+        sq = _ff_linear(Q, wql, bql)
+        pq, stq = K.fastformer_pool_fwd(sq, Q, lens, B, T, H, div)
+        QK = K.fastformer_bcast(Kt, pq, B, T)
+        sk = _ff_linear(QK, wkl, bkl)
+        pk, stk = K.fastformer_pool_fwd(sk, QK, lens, B, T, H, div)
+        WV = K.fastformer_bcast(Q, pk, B, T)
+        out = _ff_linear(WV, wt, bt, R=Q)
+        ctx.save_for_backward(hm, lens, Q, Kt, sq, pq, stq, QK, sk, pk, stk, WV, wq, bq, wk, bk, wql, bql, wkl, bkl, wt, bt)
+        ctx.dims = (B, T, Cc, H, div)
+        return out.view(B, T, Cc)
+
+    @staticmethod
+    def backward(ctx, dout):
+        hm, lens, Q, Kt, sq, pq, stq, QK, sk, pk, stk, WV, wq, bq, wk, bk, wql, bql, wkl, bkl, wt, bt = ctx.saved_tensors
+        B, T, Cc, H, div = ctx.dims
+        ng = ctx.needs_input_grad
+        dT2 = dout.contiguous().view(B * T, Cc)
+        dWV = _ff_dgrad(dT2, wt)
+        dWt, dbt = _ff_wgrad(dT2, WV, wt, bt, ng[11], ng[12])
+        dQ, dpk = K.fastformer_bcast_bwd(dWV, Q, pk, B, T, dX_in=dT2, out=None)          # dQ = dT2 (residual) + dWV * pk
+        dQK, dsk = K.fastformer_pool_bwd(dpk, pk, stk, sk, QK, lens, B, T, H, div)
+        dQK_lin = _ff_dgrad(dsk, wkl)
+        dWkl, dbkl = _ff_wgrad(dsk, QK, wkl, bkl, ng[9], ng[10])
+        dK, dpq = K.fastformer_bcast_bwd(dQK, Kt, pq, B, T, dY2=dQK_lin)
+        dQ, dsq = K.fastformer_pool_bwd(dpq, pq, stq, sq, Q, lens, B, T, H, div, dV_in=dQ)     # in place: dQ += alpha_q dpq
+        dQ = _ff_dgrad(dsq, wql, R=dQ)
+        dWql, dbql = _ff_wgrad(dsq, Q, wql, bql, ng[7], ng[8])
+        dh = _ff_dgrad(dQ, wq, R=_ff_dgrad(dK, wk)) if ng[0] else None
+        dWq, dbq = _ff_wgrad(dQ, hm, wq, bq, ng[3], ng[4])
+        dWk, dbk = _ff_wgrad(dK, hm, wk, bk, ng[5], ng[6])
+        return (dh.view(B, T, Cc) if dh is not None else None, None, None, dWq, dbq, dWk, dbk, dWql, dbql, dWkl, dbkl, dWt, dbt)
+
+
+def fast_attention(h, lens, n_heads, wq, bq, wk, bk, wql, bql, wkl, bkl, wt, bt):
+    """Q + transform(pk * Q) of the Fastformer block (see _FastAttention); lens int32 [B] valid lengths (the mask of the pooling)"""
+    return _FastAttention.apply(h, lens, n_heads, wq, bq, wk, bk, wql, bql, wkl, bkl, wt, bt)
+
+
+class _ResDrop(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, rowscale, p_drop, seed, drop_offset):
+        ctx.save_for_backward(rowscale, seed)
+        ctx.cfg = (p_drop, drop_offset)
+        return K.fastformer_resdrop(x.contiguous(), t.contiguous(), rowscale, p_drop, seed, drop_offset)
+
+    @staticmethod
+    def backward(ctx, dy):
+        rowscale, seed = ctx.saved_tensors
+        p_drop, drop_offset = ctx.cfg
+        dx, dt = K.fastformer_resdrop_bwd(dy.contiguous(), rowscale, p_drop, seed, drop_offset)
+        return dx, dt, None, None, None, None
+
+
+def residual_dropout(x, t, rowscale=None, p_drop=0.0, drop=None):
+    """y = rowscale * (x + dropout(t)): `x = x + PreNorm(fn)(x)` then `masked_fill(pad, 0)` when fn ends in a dropout that the sub-layer's
+    last GEMM cannot apply itself (Fastformer: the query residual sits inside the dropout)"""
+    seed, off = (drop.seed, drop.next_offset()) if (drop is not None and p_drop > 0) else (None, 0)
+    return _ResDrop.apply(x, t, rowscale, p_drop if seed is not None else 0.0, seed, off)

@@ -563,6 +563,32 @@ int ctts_vocoder_post(const float* x, int B, int T, int C, int k, const float* w
                       void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Fastformer additive attention (block_type "fastformer"; reference model/transformers/fastformer.py FastAttention).  Rows (b, t) run
+ * over the PADDED length T (B*T rows), columns c = h*D + j for H heads of size D (C = H*D, D a power of two <= 64, C % 64 == 0,
+ * C <= 1024).  Logits s [B*T, H] (row stride lds) come from the logit projections; lens int32 [B] are the valid lengths.
+ *   z[b,t,h] = s / div + (t < lens[b] ? -10000 : 0)          (div = sqrt(D); fp32, in this order: the reference's inverted mask)
+ *   ctts_fastformer_pool_fwd   alpha = softmax_t(z) per (b, h);  p[b, c] = sum_t alpha[b,t,h] V[b,t,c];  stats [B, H, 2] = (max, denominator)
+ *                              for the backward.  ws: ctts_fastformer_workspace_floats(B, T, H, C) floats (per-chunk partials).
+ *   ctts_fastformer_pool_bwd   dV = dV_in (NULL = 0) + alpha dp[b];  ds = alpha (sum_j V dp - sum_j p dp) / div   (dV, ds dense; dV may be dV_in)
+ *   ctts_fastformer_bcast      Y[b,t,:] = X[b,t,:] * p[b,:]    (Y dense [B*T, C])
+ *   ctts_fastformer_bcast_bwd  dy = dY1 + dY2 (NULL = 0);  dX = dX_in (NULL = 0) + dy p[b];  dp[b, c] = sum_t dy X   (dX may be dX_in)
+ *   ctts_fastformer_resdrop    backward = 0: y = rowscale * (x + dropout(t));  backward = 1 (x unused): y = rowscale * dropout(t) and
+ *                              y2 = rowscale * t, with t the incoming gradient.  rowscale [rows] or NULL; the dropout mask is the one of
+ *                              the GEMM epilogues (seed, drop_offset, index row * C + col).
+ * Reductions over T are per 32-row chunk and combined in chunk order: no atomics, bit-reproducible.  All stream-ordered, capturable. */
+size_t ctts_fastformer_workspace_floats(int B, int T, int H, int C);
+int ctts_fastformer_pool_fwd(const float* s, int64_t lds, const float* V, int64_t ldv, const int32_t* lens, float* p, float* stats,
+                             float* ws, int B, int T, int H, int C, float div, void* stream);
+int ctts_fastformer_pool_bwd(const float* dp, const float* p, const float* stats, const float* s, int64_t lds, const float* V,
+                             int64_t ldv, const int32_t* lens, const float* dV_in, float* dV, float* ds, int B, int T, int H, int C,
+                             float div, void* stream);
+int ctts_fastformer_bcast(const float* X, int64_t ldx, const float* p, float* Y, int B, int T, int C, void* stream);
+int ctts_fastformer_bcast_bwd(const float* dY1, const float* dY2, const float* X, int64_t ldx, const float* p, const float* dX_in,
+                              float* dX, float* dp, float* ws, int B, int T, int C, void* stream);
+int ctts_fastformer_resdrop(const float* x, const float* t, float* y, float* y2, int64_t rows, int C, const float* rowscale,
+                            float p_drop, const uint64_t* seed, uint32_t drop_offset, int backward, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (SURVEY.md section 8(b) `ctts_allreduce_*`, 8(e); replaces what
  * `DistributedDataParallel(model, device_ids=[rank])` does after backward in the reference: train.py:29-35,58,112).
  *   ctts_comm_unique_id  rank 0 draws CTTS_COMM_ID_BYTES opaque bytes (ncclGetUniqueId) and hands them to every rank by any side
