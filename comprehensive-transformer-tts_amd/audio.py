@@ -14,6 +14,11 @@ the reference, but not the basis.  What pins the basis is tests/test_mel_basis_c
 of librosa's own documentation (hz_to_mel / mel_to_hz / mel_frequencies(n_mels=40), all 40 values), and the triangle construction with
 the 2 / (f[i+2] - f[i]) area normalisation against its published definition.  Swap in librosa's array (`stft.mel_basis.copy_(...)`)
 where it is available.
+
+Griffin-Lim (reference audio/stft.py:22-134 `STFT`, audio/audio_processing.py `griffin_lim` / `window_sumsquare` /
+`dynamic_range_*`, audio/tools.py:18-34 `inv_mel_spec`): `STFT.transform` / `inverse` and every Griffin-Lim iteration run on
+csrc/griffinlim.hip (a 1024-point real FFT per frame; one launch per iteration).  Supported: filter_length 1024, hop 256,
+win_length 1024, hann - an `STFT` of other sizes can be built (so can `TacotronSTFT`), its methods raise.
 """
 import math
 
@@ -76,6 +81,146 @@ def windowed_dft_basis(n_fft, win_length):
     return (basis.astype(np.float32) * win.astype(np.float32)[None, :]).astype(np.float32)
 
 
+def dynamic_range_compression(x, C=1, clip_val=1e-5):
+    """audio_processing.py:85-91: log(clamp(x, clip_val) * C) (elementwise torch, any device - not a hot path)"""
+    return torch.log(torch.clamp(x, min=clip_val) * C)
+
+
+def dynamic_range_decompression(x, C=1):
+    """audio_processing.py:94-100: exp(x) / C (elementwise torch, any device)"""
+    return torch.exp(x) / C
+
+
+def window_sumsquare(window, n_frames, hop_length, win_length, n_fft, dtype=np.float32, norm=None):
+    """audio_processing.py:7-63 (librosa 0.6's window_sumsquare): the sum-square envelope [n_fft + hop_length (n_frames - 1)] of the
+    window at the given hop, a host numpy helper like the reference's.  norm: only None (the reference's default and only use: librosa's
+    normalize(norm=None) returns its input).  STFT.inverse does not call it: the kernels sum the same envelope per sample."""
+    from scipy.signal import get_window
+    if norm is not None:
+        raise NotImplementedError("window_sumsquare: only norm=None (what STFT.inverse uses)")
+    win_length = n_fft if win_length is None else win_length
+    lpad = (n_fft - win_length) // 2
+    w2 = np.zeros(n_fft)                                   # squared window, centred in n_fft
+    w2[lpad:lpad + win_length] = get_window(window, win_length, fftbins=True) ** 2
+    starts = hop_length * np.arange(max(int(n_frames), 0))
+    env = np.zeros(max(n_fft + hop_length * (int(n_frames) - 1), 0))
+    if len(starts):
+        np.add.at(env, starts[:, None] + np.arange(n_fft)[None, :], np.broadcast_to(w2, (len(starts), n_fft)))
+    return env.astype(dtype)
+
+
+def _lens_arg(lens, B, lo, hi, what, dev):
+    """per-utterance lengths of a ragged batch: a host sequence (checked against [lo, hi]) or an int32 device tensor (the kernels clamp)"""
+    if lens is None:
+        return None
+    if torch.is_tensor(lens) and lens.is_cuda:
+        if lens.numel() != B:                              # the kernels read one length per utterance: no fewer, no more
+            raise ValueError(f"{what}: {lens.numel()} lengths for a batch of {B}")
+        return lens.to(torch.int32).contiguous().view(B)
+    v = [int(n) for n in (lens.tolist() if torch.is_tensor(lens) else lens)]
+    if len(v) != B:
+        raise ValueError(f"{what}: {len(v)} lengths for a batch of {B}")
+    if min(v) < lo or max(v) > hi:
+        raise ValueError(f"{what}: lengths must lie in [{lo}, {hi}], got {min(v)} .. {max(v)}")
+    return torch.tensor(v, dtype=torch.int32).to(dev)
+
+
+class STFT(nn.Module):
+    """Drop-in `audio.stft.STFT` (stft.py:22-134) on csrc/griffinlim.hip.  transform(x [B,N]) -> (magnitude, phase) [B,513,F],
+    F = 1 + N // 256; inverse(magnitude, phase) -> [B,1,256 (F - 1)]; forward = inverse(transform(x)).  Device tensors only.
+    Optional `lens` (ragged batches): samples per utterance for transform, frames per utterance for inverse; every utterance gets what a
+    B = 1 call on its own slice gives (reflection at its own end); positions past its end are 0."""
+
+    def __init__(self, filter_length, hop_length, win_length, window="hann"):
+        super().__init__()
+        self.filter_length, self.hop_length, self.win_length, self.window = filter_length, hop_length, win_length, window
+        if window is not None:
+            assert filter_length >= win_length
+        self.supported = (filter_length, hop_length, win_length, window) == (1024, 256, 1024, "hann")
+        self.register_buffer("_win", torch.from_numpy(padded_window(filter_length, min(win_length, filter_length))), persistent=False)
+        self._ws = None
+
+    def _apply(self, fn, *args, **kwargs):
+        # build the kernel workspace (a launch) as soon as the module lands on the device, outside any graph capture
+        out = super()._apply(fn, *args, **kwargs)
+        self._ws = None
+        if self.supported and self._win.is_cuda and not torch.cuda.is_current_stream_capturing():
+            from . import kernels as K
+            self._ws = K.griffinlim_prepare(self._win)
+        return out
+
+    def _workspace(self, t, name):
+        if not self.supported:
+            raise NotImplementedError(f"STFT (ctts_amd) runs filter_length 1024, hop 256, win_length 1024, hann only; built with "
+                                      f"{self.filter_length} / {self.hop_length} / {self.win_length} / {self.window}")
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f"STFT (ctts_amd) computes on the MI355X: pass {name} as a device tensor")
+        from . import kernels as K
+        if self._ws is None or self._ws.device != t.device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("STFT (ctts_amd): move the module to the device (or call it once) before capturing a graph - its "
+                                   "workspace is built by a kernel launch, which a capture would only record")
+            if self._win.device != t.device:
+                self.to(t.device)                          # builds the workspace (_apply)
+            if self._ws is None or self._ws.device != t.device:
+                self._ws = K.griffinlim_prepare(self._win)
+        return self._ws
+
+    def transform(self, input_data, lens=None):
+        from . import kernels as K
+        ws = self._workspace(input_data, "input_data")
+        B, N = input_data.size(0), input_data.size(1)
+        if N <= self.filter_length // 2:
+            raise ValueError(f"STFT.transform: reflect padding needs more than {self.filter_length // 2} samples, got {N}")
+        self.num_samples = N
+        x = input_data.reshape(B, N).float().contiguous()
+        return K.stft_transform(x, ws, _lens_arg(lens, B, self.filter_length // 2 + 1, N, "STFT.transform lens", x.device))
+
+    def _frames(self, magnitude, lens, fmin):
+        """fmin: 2 for inverse (256 (F - 1) samples out), 4 for Griffin-Lim (its transform needs more than n_fft/2 samples)"""
+        B, _, F = magnitude.shape
+        if F < fmin:
+            raise ValueError(f"STFT (ctts_amd): needs at least {fmin} frames here, got {F}")
+        return _lens_arg(lens, B, fmin, F, "frame lens", magnitude.device)
+
+    def inverse(self, magnitude, phase, lens=None):
+        from . import kernels as K
+        ws = self._workspace(magnitude, "magnitude")
+        self._workspace(phase, "phase")
+        frames = self._frames(magnitude, lens, 2)
+        Y, _ = K.istft_frames(magnitude.float().contiguous(), phase.float().contiguous(), ws, frames)
+        return K.istft_ola(Y, ws, frames).unsqueeze(1)
+
+    def forward(self, input_data):
+        self.magnitude, self.phase = self.transform(input_data)
+        return self.inverse(self.magnitude, self.phase)
+
+
+def griffin_lim(magnitudes, stft_fn, n_iters=30, angles=None, lens=None):
+    """audio_processing.py:66-82 on the kernels: magnitudes [B,513,F] (device) -> signal [B, 256 (F - 1)].
+    angles=None draws the initial phase from numpy's GLOBAL generator exactly like the reference (np.random.seed(s) reproduces a
+    reference run); an explicit device tensor [B,513,F] skips the host draw (and is capturable).  lens: frames per utterance of a ragged
+    batch.  Launches: one inverse (frames), one per iteration (csrc/griffinlim.hip gl_iter_kernel, ping-pong frame buffers), one
+    overlap-add; no host synchronisation."""
+    from . import kernels as K
+    if not isinstance(stft_fn, STFT):
+        raise TypeError("griffin_lim (ctts_amd): stft_fn must be a ctts_amd.audio.STFT (e.g. TacotronSTFT.stft_fn)")
+    ws = stft_fn._workspace(magnitudes, "magnitudes")
+    frames = stft_fn._frames(magnitudes, lens, 4)
+    if angles is None:
+        angles = np.angle(np.exp(2j * np.pi * np.random.rand(*magnitudes.size())))
+        angles = torch.from_numpy(angles.astype(np.float32)).to(magnitudes.device)
+    else:
+        stft_fn._workspace(angles, "angles")
+    Y, magT = K.istft_frames(magnitudes.float().contiguous(), angles.float().contiguous(), ws, frames, want_magT=n_iters > 0)
+    if n_iters > 0:
+        Y2 = torch.empty_like(Y)
+        for _ in range(n_iters):
+            K.griffinlim_iter(Y, magT, ws, Y2, frames)
+            Y, Y2 = Y2, Y
+    return K.istft_ola(Y, ws, frames)
+
+
 class TacotronSTFT(nn.Module):
     def __init__(self, filter_length, hop_length, win_length, n_mel_channels, sampling_rate, mel_fmin, mel_fmax):
         super().__init__()
@@ -89,6 +234,7 @@ class TacotronSTFT(nn.Module):
         self.register_buffer("_mel_basis_padded", torch.from_numpy(padded), persistent=False)
         self.register_buffer("_dft_basis", torch.from_numpy(windowed_dft_basis(filter_length, win_length)), persistent=False)
         self.register_buffer("_window", torch.from_numpy(padded_window(filter_length, win_length)), persistent=False)
+        self.stft_fn = STFT(filter_length, hop_length, win_length)      # non-persistent buffers only: state_dict stays ['mel_basis']
         self._fft_ws = None          # device workspace of the FFT kernel (twiddles, transposed filterbank), built on first use
         self.use_fft = filter_length == 1024 and n_mel_channels <= 96
         nz = np.nonzero(np.abs(mel).sum(0))[0]
@@ -99,6 +245,14 @@ class TacotronSTFT(nn.Module):
         # hot path - the flag is looked at without waiting at the next call, or on demand with check_range() (call it before using the
         # last result).
         self.strict_range = True
+
+    def spectral_normalize(self, magnitudes):
+        """stft.py:158-160"""
+        return dynamic_range_compression(magnitudes)
+
+    def spectral_de_normalize(self, magnitudes):
+        """stft.py:162-164"""
+        return dynamic_range_decompression(magnitudes)
 
     # ---- the reference asserts min(y) >= -1 and max(y) <= 1 on the host before computing (stft.py:177-178): two reductions and a
     # device -> host synchronisation per call, which halves the throughput of a 50 us kernel.  Here the kernel raises a flag while it
@@ -203,3 +357,18 @@ class TacotronSTFT(nn.Module):
 def get_mel_from_wav(audio, _stft):
     """audio/tools.py:8-15: one utterance (numpy) -> (mel [n_mel, F], energy [F]) float32 numpy, input clipped to [-1, 1]"""
     return _stft.mel_spectrograms_ragged([audio])[0]
+
+
+def inv_mel_spec(mel, out_filename, _stft, griffin_iters=60):
+    """audio/tools.py:18-34: log-mel [n_mel, F] (device tensor) -> float32 wav at _stft.sampling_rate through Griffin-Lim, bug for bug:
+    exp(mel) times the filterbank itself (not a pseudo-inverse), * 1000, the last frame dropped.  One deliberate deviation: the reference
+    reads `_stft._stft_fn`, which does not exist (AttributeError); this version uses `_stft.stft_fn`."""
+    from scipy.io.wavfile import write
+    if not torch.is_tensor(mel) or not mel.is_cuda:
+        raise RuntimeError("inv_mel_spec (ctts_amd) computes on the MI355X: pass the mel as a device tensor")
+    if _stft.mel_basis.device != mel.device:
+        _stft.to(mel.device)
+    # spectral_de_normalize (exp, C = 1), the filterbank applied transposed, the fixed gain; drop the last frame, then Griffin-Lim
+    spec = (torch.exp(mel).t() @ _stft.mel_basis).t().unsqueeze(0) * 1000.0     # [1, 513, F]
+    wav = griffin_lim(spec[:, :, :-1], _stft.stft_fn, griffin_iters)[0]
+    write(out_filename, _stft.sampling_rate, wav.cpu().numpy())

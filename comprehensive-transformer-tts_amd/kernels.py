@@ -1385,3 +1385,69 @@ def fastformer_resdrop_bwd(dy, rowscale=None, p_drop=0.0, seed=None, drop_offset
     _lib.check(_lib.load().ctts_fastformer_resdrop(None, _p(_f32c(dy, "dy")), _p(dt), _p(dx), dy.numel() // Cc, int(Cc), _p(rowscale),
                                                    float(p_drop), _p(seed), int(drop_offset), 1, _stream()), "ctts_fastformer_resdrop")
     return dx, dt
+
+
+# ---- Griffin-Lim / STFT (csrc/griffinlim.hip) ---------------------------------------------------------------------------------
+GL_NFFT, GL_HOP, GL_NBINS = 1024, 256, 513
+
+
+def griffinlim_prepare(window):
+    """window [1024] float32 (device) -> workspace of the STFT / Griffin-Lim kernels (twiddles, window, window^2)"""
+    lib = _lib.load()
+    ws = torch.empty(lib.ctts_griffinlim_workspace_bytes(GL_NFFT, GL_HOP) // 4, dtype=torch.float32, device=window.device)
+    _lib.check(lib.ctts_griffinlim_prepare(_p(_f32c(window, "window")), GL_NFFT, GL_HOP, _p(ws), _stream()), "ctts_griffinlim_prepare")
+    return ws
+
+
+def _frames_arg(frames):
+    if frames is None:
+        return None
+    if not frames.is_cuda or frames.dtype != torch.int32 or not frames.is_contiguous():
+        raise _lib.CttsError("frames / lens: expected a contiguous int32 device tensor")
+    return frames
+
+
+def stft_transform(x, ws, lens=None):
+    """x [B,N] float32 -> (magnitude, phase) [B,513,F], F = 1 + N // 256 (STFT.transform, audio/stft.py:59-88); lens: int32 [B] samples"""
+    B, N = x.shape
+    F = 1 + N // GL_HOP
+    mag = torch.empty(B, GL_NBINS, F, dtype=torch.float32, device=x.device)
+    phase = torch.empty_like(mag)
+    lib = _lib.load()
+    _lib.check(lib.ctts_stft_transform(_p(_f32c(x, "x")), _p(_frames_arg(lens)), _p(ws), _p(mag), _p(phase), GL_NBINS * F, F, 1,
+                                       B, N, GL_NFFT, GL_HOP, _stream()), "ctts_stft_transform")
+    return mag, phase
+
+
+def istft_frames(mag, phase, ws, frames=None, want_magT=False):
+    """(mag, phase) [B,513,F] contiguous -> (Y [B,F,1024] windowed inverse-DFT frames, frame-major magnitude copy [B,F,513] or None)"""
+    B, nb, F = mag.shape
+    if nb != GL_NBINS or phase.shape != mag.shape:
+        raise _lib.CttsError(f"istft_frames: expected magnitude and phase [B, 513, F], got {tuple(mag.shape)} / {tuple(phase.shape)}")
+    Y = torch.empty(B, F, GL_NFFT, dtype=torch.float32, device=mag.device)
+    magT = torch.empty(B, F, GL_NBINS, dtype=torch.float32, device=mag.device) if want_magT else None
+    lib = _lib.load()
+    _lib.check(lib.ctts_istft_frames(_p(_f32c(mag, "magnitude")), _p(_f32c(phase, "phase")), GL_NBINS * F, F, 1, _p(_frames_arg(frames)),
+                                     _p(ws), _p(Y), _p(magT), B, F, GL_NFFT, GL_HOP, _stream()), "ctts_istft_frames")
+    return Y, magT
+
+
+def griffinlim_iter(Y_in, magT, ws, Y_out, frames=None):
+    """one Griffin-Lim iteration on the frame buffers (Y_in -> Y_out, [B,F,1024]); magT [B,F,513] the target magnitude"""
+    B, F, _ = Y_in.shape
+    lib = _lib.load()
+    _lib.check(lib.ctts_griffinlim_iter(_p(_f32c(Y_in, "Y_in")), _p(_f32c(magT, "magT")), _p(_frames_arg(frames)), _p(ws),
+                                        _p(_f32c(Y_out, "Y_out")), B, F, GL_NFFT, GL_HOP, _stream()), "ctts_griffinlim_iter")
+    return Y_out
+
+
+def istft_ola(Y, ws, frames=None, out=None):
+    """Y [B,F,1024] -> waveform [B, 256 (F - 1)] (overlap-add, window-sum division, * 4, crop)"""
+    B, F, _ = Y.shape
+    L = GL_HOP * (F - 1)
+    if out is None:
+        out = torch.empty(B, L, dtype=torch.float32, device=Y.device)
+    lib = _lib.load()
+    _lib.check(lib.ctts_istft_ola(_p(_f32c(Y, "Y")), _p(_frames_arg(frames)), _p(ws), _p(_f32c(out, "out")), out.shape[-1], B, F,
+                                  GL_NFFT, GL_HOP, _stream()), "ctts_istft_ola")
+    return out

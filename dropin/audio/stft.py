@@ -1,2 +1,2 @@
-"""`audio.stft.TacotronSTFT` (`/root/reference/audio/stft.py:137-185`) -> ctts_amd.audio.TacotronSTFT (csrc/mel.hip)"""
-from ctts_amd.audio import TacotronSTFT  # noqa: F401
+"""`audio.stft.TacotronSTFT` / `audio.stft.STFT` (the reference's `audio/stft.py:22-185`) -> ctts_amd.audio (csrc/mel.hip, csrc/griffinlim.hip)"""
+from ctts_amd.audio import STFT, TacotronSTFT  # noqa: F401

@@ -1,2 +1,2 @@
-"""`audio.tools.get_mel_from_wav` (`/root/reference/audio/tools.py:8-15`) -> ctts_amd.audio.get_mel_from_wav"""
-from ctts_amd.audio import get_mel_from_wav  # noqa: F401
+"""`audio.tools.get_mel_from_wav` / `inv_mel_spec` (the reference's `audio/tools.py:8-34`) -> ctts_amd.audio"""
+from ctts_amd.audio import get_mel_from_wav, inv_mel_spec  # noqa: F401

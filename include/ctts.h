@@ -589,6 +589,33 @@ int ctts_fastformer_resdrop(const float* x, const float* t, float* y, float* y2,
                             float p_drop, const uint64_t* seed, uint32_t drop_offset, int backward, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Griffin-Lim vocoder (csrc/griffinlim.hip): audio/stft.py:22-134 STFT.transform / inverse and audio/audio_processing.py:66-82
+ * griffin_lim on a 1024-point real FFT per frame (one wave per frame, no dense basis).  Built for n_fft = 1024, hop = 256 only (other
+ * sizes return an error); the analysis / synthesis window is the [1024] table handed to the prepare call (periodic hann zero-padded to
+ * n_fft in the product).  Every entry point is stream-ordered, allocation-free, atomic-free (bit-reproducible) and capturable.
+ *   workspace  griffinlim_workspace_bytes() bytes: twiddles, window, window^2; filled once by griffinlim_prepare(window [1024]).
+ *   transform  x [B,N] (N > 512) -> mag, phase: element (b, k, f) at b sb + k sk + f sf, k < 513, F = 1 + N / 256.  lens (device int32
+ *              [B] or NULL): samples per utterance; each reflects at its own end, frames past 1 + lens[b] / 256 are written as 0.
+ *   istft_frames   (mag, phase) (same strides) -> Y [B][F][1024], the windowed inverse-DFT frames before overlap-add; magT (optional,
+ *              [B][F][513]) receives a frame-major copy of mag, the operand of griffinlim_iter.
+ *   griffinlim_iter  Y_in -> Y_out (distinct buffers): overlap-add of Y_in, transform with reflect padding, magnitude replaced by magT
+ *              (phase kept; (mag, 0) where |X| = 0), inverse - one Griffin-Lim iteration.
+ *   istft_ola  Y -> out [B, ld_out >= 256 (F - 1)]: overlap-add in ascending frame order, / window_sumsquare where > FLT_MIN, * 4, crop
+ *              512 at both ends; samples past 256 (frames[b] - 1) are written as 0.
+ * frames (device int32 [B] or NULL = F): frames per utterance of a ragged batch.  istft_frames / istft_ola need F >= 2 and clamp
+ *   frames[b] to [2, F]; griffinlim_iter needs F >= 4 and clamps to [4, F] (its transform needs more than n_fft/2 samples). */
+size_t ctts_griffinlim_workspace_bytes(int n_fft, int hop);
+int ctts_griffinlim_prepare(const float* window, int n_fft, int hop, float* workspace, void* stream);
+int ctts_stft_transform(const float* x, const int32_t* lens, const float* workspace, float* mag, float* phase, int64_t sb, int64_t sk,
+                        int64_t sf, int B, int N, int n_fft, int hop, void* stream);
+int ctts_istft_frames(const float* mag, const float* phase, int64_t sb, int64_t sk, int64_t sf, const int32_t* frames,
+                      const float* workspace, float* Y, float* magT, int B, int F, int n_fft, int hop, void* stream);
+int ctts_griffinlim_iter(const float* Y_in, const float* magT, const int32_t* frames, const float* workspace, float* Y_out, int B, int F,
+                         int n_fft, int hop, void* stream);
+int ctts_istft_ola(const float* Y, const int32_t* frames, const float* workspace, float* out, int64_t ld_out, int B, int F, int n_fft,
+                   int hop, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (SURVEY.md section 8(b) `ctts_allreduce_*`, 8(e); replaces what
  * `DistributedDataParallel(model, device_ids=[rank])` does after backward in the reference: train.py:29-35,58,112).
  *   ctts_comm_unique_id  rank 0 draws CTTS_COMM_ID_BYTES opaque bytes (ncclGetUniqueId) and hands them to every rank by any side
