@@ -61,6 +61,7 @@ class VconvDesc(C.Structure):
         ("out", _vp),
         ("alpha", _f32), ("beta", _f32),
         ("bf16_split", _i32),
+        ("lens", _vp), ("len_mul", _i32),
     ]
 
 
@@ -160,6 +161,7 @@ _SIGNATURES = {
     "ctts_softmax_rect_bwd": [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp],
     "ctts_vocoder_conv": [C.POINTER(VconvDesc), _vp],
     "ctts_vocoder_post": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _f32, _vp, _vp],
+    "ctts_vocoder_post_ragged": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _f32, _vp, _vp, C.c_int, _vp],
     "ctts_fastformer_pool_fwd": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, _vp],
     "ctts_fastformer_pool_bwd": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, _vp],
     "ctts_fastformer_bcast": [_vp, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp],

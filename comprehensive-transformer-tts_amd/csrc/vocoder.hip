@@ -15,7 +15,13 @@
 //   Arithmetic (include/ctts.h ctts_vocoder_conv): X6 = the exact three-way bf16 split (planes_common.h spl_one) with the six cross terms on
 //   v_mfma_f32_32x32x16_bf16, fp32 accumulation; otherwise exact fp32 on v_mfma_f32_32x32x2_f32.  No atomics: every output element is
 //   produced by one lane in a fixed order.
-// vpost_kernel: conv_post (Cout = 1, models.py:161-163) - leaky_relu(0.01) on load, 7-tap dot product on the VALU, + bias, tanh.
+//   Length-aware batches (include/ctts.h, lens / len_mul): a workgroup reads lens[b] once (wave-uniform) and its utterance's own row
+//   count Tb = min(lens[b] len_mul, T) takes T's place in the staging, the halo, the epilogue's row bound (R and beta * out included)
+//   and the transposed conv's row range and phase scatter; a tile at or beyond its utterance's end returns before it stages anything.
+//   The grid is still sized by the padded T and anchored at row 0 of each utterance, so a tile computes bit for bit what the same tile
+//   of a B = 1 call on the unpadded utterance computes.  Rows beyond Tb are not stored (nothing reads them).
+// vpost_kernel: conv_post (Cout = 1, models.py:161-163) - leaky_relu(0.01) on load, 7-tap dot product on the VALU, + bias, tanh;
+//   with lens it writes exact zeros from row Tb on (whole tiles beyond the end without staging).
 #include "ctts_common.h"
 #include "planes_common.h"
 
@@ -41,7 +47,15 @@ struct VcParams {
   int act_in; float slope; int vec;
   const float* w; const uint16_t* wp; const float* bias; const float* R; float* out;
   float alpha, beta;
+  const int* lens; int len_mul, mextra;     // ragged: utterance b's input has min(lens[b] len_mul, T) rows; Mrows = T + mextra
 };
+
+// rows of utterance b's signal at a layer whose dense length is T: min(max(lens[b], 0) len_mul, T); lens == NULL: T (wave-uniform)
+__device__ __forceinline__ int vc_rows(const int* lens, int b, int len_mul, int T) {
+  if (!lens) return T;
+  const long n = (long)max(lens[b], 0) * len_mul;
+  return n < (long)T ? (int)n : T;
+}
 
 __device__ __forceinline__ int x6sw(int row, int c) { return c ^ ((row >> 2) & 3); }
 __device__ __forceinline__ int f32sw(int row, int c) { return c ^ ((row >> 1) & 7); }
@@ -61,6 +75,9 @@ __global__ __launch_bounds__(256, 2) void vconv_kernel(const VcParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
   const int b = blockIdx.z, m0 = blockIdx.x * VC_BM, col0 = blockIdx.y * BN;
   const int wm0 = (wave / WAVES_N) * (MT * 32), wn0 = (wave % WAVES_N) * (NT * 32);
+  // ragged (include/ctts.h): the utterance's own length replaces T everywhere below; a tile at or beyond its end has nothing to do
+  const int Tb = vc_rows(p.lens, b, p.len_mul, p.T), Mb = Tb + p.mextra, Toutb = p.u ? Tb * p.u : Tb;
+  if (Tb == 0 || m0 >= Mb) return;
   const int p0 = p.row_off + m0;                      // position of tile row 0
   const int nchunks = p.cin_pad >> 5, taps = p.taps;
   const long kp = (long)taps * p.cin_pad;             // packed weight row length
@@ -107,13 +124,13 @@ __global__ __launch_bounds__(256, 2) void vconv_kernel(const VcParams p) {
       }
     }
   };
-  // input rows p0 + in_off + i (i < arows), channels chunk * 32 .. + 31, activated, zero outside [0, T) x [0, Cin)
+  // input rows p0 + in_off + i (i < arows), channels chunk * 32 .. + 31, activated, zero outside [0, T) x [0, Cin)   (T = the utterance's Tb)
   auto stage_a = [&](int chunk) {
     const int c4 = tid & 7, cbase = chunk * 32 + c4 * 4;
     for (int i = tid >> 3; i < arows; i += 32) {
       const int ti = p0 + p.in_off + i;
       float v[4] = {0.f, 0.f, 0.f, 0.f};
-      if (ti >= 0 && ti < p.T) {
+      if (ti >= 0 && ti < Tb) {
         const float* src = xb + (long)ti * p.sxt;
         if (p.vec) {
           if (cbase < p.Cin) {
@@ -236,10 +253,10 @@ __global__ __launch_bounds__(256, 2) void vconv_kernel(const VcParams p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int ml = wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (m0 + ml >= p.Mrows) continue;
+        if (m0 + ml >= Mb) continue;
         const int pos = p0 + ml;
         const int to = p.u ? pos * p.u + ph - p.pad : pos;
-        if (to < 0 || to >= p.Tout) continue;
+        if (to < 0 || to >= Toutb) continue;
         const long idx = obase + (long)to * p.Cout + co;
         float v = acc[i][j][r] + bv;
         if (p.R) v += p.R[idx];
@@ -253,19 +270,26 @@ __global__ __launch_bounds__(256, 2) void vconv_kernel(const VcParams p) {
 constexpr int VP_ROWS = 256, VP_PITCH = 33;
 
 // out[b, 0, t] = tanh(bias + sum_{tap, c} leaky_relu(x[b, t + tap - (k - 1) / 2, c], slope) w[tap][c]); x [B, T, C] dense
+// ragged (lens != NULL): rows at or beyond Tb = min(lens[b] len_mul, T) read as zero and out[b, 0, Tb ..] = 0
 __global__ __launch_bounds__(256) void vpost_kernel(const float* __restrict__ x, int T, int C, int k, const float* __restrict__ w,
-                                                    const float* __restrict__ bias, float slope, float* __restrict__ out) {
+                                                    const float* __restrict__ bias, float slope, float* __restrict__ out,
+                                                    const int* __restrict__ lens, int len_mul) {
   extern __shared__ float xs[];
   const int b = blockIdx.y, t0 = blockIdx.x * VP_ROWS, tid = threadIdx.x, half = (k - 1) / 2;
   const int rows = VP_ROWS + k - 1;
   const float* xb = x + (long)b * T * C;
+  const int Tb = vc_rows(lens, b, len_mul, T);
+  if (t0 >= Tb) {                          // a tile beyond the utterance's end: the zeros of the result, nothing staged
+    if (t0 + tid < T) out[(long)b * T + t0 + tid] = 0.f;
+    return;
+  }
   float acc = 0.f;
   for (int c0 = 0; c0 < C; c0 += 32) {
     __syncthreads();
     for (int e = tid; e < rows * 32; e += 256) {
       const int r = e >> 5, c = e & 31, t = t0 - half + r;
       float v = 0.f;
-      if (t >= 0 && t < T && c0 + c < C) {
+      if (t >= 0 && t < Tb && c0 + c < C) {
         v = xb[(long)t * C + c0 + c];
         v = v > 0.f ? v : v * slope;
       }
@@ -280,7 +304,7 @@ __global__ __launch_bounds__(256) void vpost_kernel(const float* __restrict__ x,
     }
   }
   const int t = t0 + tid;
-  if (t < T) out[(long)b * T + t] = tanhf(acc + bias[0]);
+  if (t < T) out[(long)b * T + t] = t < Tb ? tanhf(acc + bias[0]) : 0.f;
 }
 
 }  // namespace
@@ -296,6 +320,8 @@ extern "C" int ctts_vocoder_conv(const ctts_vconv_desc* dp, void* stream) {
   p.T = d.T; p.Cin = d.Cin; p.cin_pad = (d.Cin + 31) / 32 * 32; p.Cout = d.Cout;
   p.act_in = d.act_in; p.slope = d.slope;
   p.w = d.w; p.wp = d.w_planes; p.bias = d.bias; p.R = d.R; p.out = d.out; p.alpha = d.alpha; p.beta = d.beta;
+  CTTS_REQUIRE(!d.lens || d.len_mul >= 1, "ctts_vocoder_conv: lens needs len_mul >= 1 (len_mul=%d)", d.len_mul);
+  p.lens = d.lens; p.len_mul = d.len_mul;
   const int u = d.transposed_u;
   if (u == 0) {
     CTTS_REQUIRE(d.k % 2 == 1 && d.dil >= 1, "ctts_vocoder_conv: Conv1d needs an odd k and dil >= 1 (k=%d dil=%d)", d.k, d.dil);
@@ -310,6 +336,7 @@ extern "C" int ctts_vocoder_conv(const ctts_vconv_desc* dp, void* stream) {
     p.taps = J; p.dil = 1; p.in_off = -(J - 1); p.row_off = qlo; p.Mrows = qhi - qlo;
     p.N = u * d.Cout; p.u = u; p.pad = pad; p.Tout = d.T * u;
   }
+  p.mextra = p.Mrows - d.T;               // the grid is sized by the padded T: no host read of lens
   CTTS_REQUIRE((p.taps - 1) * p.dil <= VC_HALO_MAX, "ctts_vocoder_conv: halo (taps - 1) x dil = %d exceeds %d", (p.taps - 1) * p.dil,
                VC_HALO_MAX);
   const bool x6 = d.bf16_split != 0;
@@ -333,14 +360,25 @@ extern "C" int ctts_vocoder_conv(const ctts_vconv_desc* dp, void* stream) {
   return 0;
 }
 
+static int vpost_launch(const char* what, const float* x, int B, int T, int C, int k, const float* w, const float* bias, float slope,
+                        float* out, const int32_t* lens, int len_mul, void* stream) {
+  CTTS_REQUIRE(x && w && bias && out && B >= 1 && T >= 1 && C >= 1 && k >= 1 && k % 2 == 1, "%s: bad arguments (B=%d T=%d C=%d k=%d)", what,
+               B, T, C, k);
+  const size_t lds = (size_t)(VP_ROWS + k - 1) * VP_PITCH * sizeof(float);
+  CTTS_REQUIRE(lds <= 64 * 1024, "%s: k=%d too large", what, k);
+  dim3 grid((T + VP_ROWS - 1) / VP_ROWS, B);
+  hipLaunchKernelGGL(vpost_kernel, grid, dim3(256), lds, (hipStream_t)stream, x, T, C, k, w, bias, slope, out, lens, len_mul);
+  CTTS_CHECK_LAUNCH(what);
+  return 0;
+}
+
 extern "C" int ctts_vocoder_post(const float* x, int B, int T, int C, int k, const float* w, const float* bias, float slope, float* out,
                                  void* stream) {
-  CTTS_REQUIRE(x && w && bias && out && B >= 1 && T >= 1 && C >= 1 && k >= 1 && k % 2 == 1,
-               "ctts_vocoder_post: bad arguments (B=%d T=%d C=%d k=%d)", B, T, C, k);
-  const size_t lds = (size_t)(VP_ROWS + k - 1) * VP_PITCH * sizeof(float);
-  CTTS_REQUIRE(lds <= 64 * 1024, "ctts_vocoder_post: k=%d too large", k);
-  dim3 grid((T + VP_ROWS - 1) / VP_ROWS, B);
-  hipLaunchKernelGGL(vpost_kernel, grid, dim3(256), lds, (hipStream_t)stream, x, T, C, k, w, bias, slope, out);
-  CTTS_CHECK_LAUNCH("ctts_vocoder_post");
-  return 0;
+  return vpost_launch("ctts_vocoder_post", x, B, T, C, k, w, bias, slope, out, nullptr, 1, stream);
+}
+
+extern "C" int ctts_vocoder_post_ragged(const float* x, int B, int T, int C, int k, const float* w, const float* bias, float slope,
+                                        float* out, const int32_t* lens, int len_mul, void* stream) {
+  CTTS_REQUIRE(lens && len_mul >= 1, "ctts_vocoder_post_ragged: lens and len_mul >= 1 are required (len_mul=%d)", len_mul);
+  return vpost_launch("ctts_vocoder_post_ragged", x, B, T, C, k, w, bias, slope, out, lens, len_mul, stream);
 }

@@ -1254,11 +1254,23 @@ def vocoder_pack_weight(weight, transposed_u=0, planes=None):
     return packed, (split_planes([packed])[0] if use else None)
 
 
+def _vocoder_lens(lens, len_mul, B, what):
+    """the (pointer, multiplier) pair of a ragged vocoder launch: lens a device int32 [B] tensor (contiguous) or None = dense"""
+    if lens is None:
+        return None, 0
+    if not (torch.is_tensor(lens) and lens.is_cuda and lens.dtype == torch.int32 and tuple(lens.shape) == (B,) and lens.is_contiguous()):
+        raise _lib.CttsError(f"{what}: lens must be a contiguous device int32 tensor of shape ({B},)")
+    if int(len_mul) < 1:
+        raise _lib.CttsError(f"{what}: len_mul must be >= 1, got {len_mul}")
+    return _p(lens), int(len_mul)
+
+
 def vocoder_conv(x, w, w_planes, Cin, Cout, k, dil=1, transposed_u=0, slope=None, bias=None, R=None, out=None, alpha=1.0, beta=0.0,
-                 bf16_split=None):
+                 bf16_split=None, lens=None, len_mul=1):
     """One generator layer (include/ctts.h ctts_vocoder_conv).  x: [B, T, Cin] with any strides (fp32); w / w_planes from
     vocoder_pack_weight; slope: leaky_relu slope applied to x on load, or None.  -> out [B, T_out, Cout] (T_out = T or T u):
-    out = beta * out + alpha * (conv + bias + R)."""
+    out = beta * out + alpha * (conv + bias + R).  lens (device int32 [B]) / len_mul: the length-aware form - utterance b's input has
+    min(lens[b] len_mul, T) rows, computed as a B = 1 call on them would; output rows beyond its end are left unwritten."""
     if x.dtype != torch.float32 or x.dim() != 3:
         raise _lib.CttsError(f"vocoder_conv: x must be a 3-D float32 tensor [B, T, Cin], got {x.dtype} {tuple(x.shape)}")
     B, T, cin = x.shape
@@ -1292,16 +1304,24 @@ def vocoder_conv(x, w, w_planes, Cin, Cout, k, dil=1, transposed_u=0, slope=None
     d.out = _p(_f32c(out, "out"))
     d.alpha, d.beta = float(alpha), float(beta)
     d.bf16_split = split
+    d.lens, d.len_mul = _vocoder_lens(lens, len_mul, B, "vocoder_conv")
     _lib.check(_lib.load().ctts_vocoder_conv(C.byref(d), _stream()), "ctts_vocoder_conv")
     return out
 
 
-def vocoder_post(x, w, bias, slope=0.01, out=None):
-    """conv_post + tanh (include/ctts.h ctts_vocoder_post): x [B, T, C] dense, w [k, C] (= weight[0].T), bias [1] -> [B, 1, T]."""
+def vocoder_post(x, w, bias, slope=0.01, out=None, lens=None, len_mul=1):
+    """conv_post + tanh (include/ctts.h ctts_vocoder_post): x [B, T, C] dense, w [k, C] (= weight[0].T), bias [1] -> [B, 1, T].
+    lens (device int32 [B]) / len_mul: ctts_vocoder_post_ragged - out[b, 0, lens[b] len_mul:] = 0, rows there are never read."""
     B, T, Cc = x.shape
     k = w.shape[0]
     if out is None:
         out = torch.empty(B, 1, T, dtype=torch.float32, device=x.device)
+    if lens is not None:
+        lp, lm = _vocoder_lens(lens, len_mul, B, "vocoder_post")
+        _lib.check(_lib.load().ctts_vocoder_post_ragged(_p(_f32c(x, "x")), B, T, Cc, int(k), _p(_f32c(w, "w")), _p(_f32c(bias, "bias")),
+                                                        float(slope), _p(_f32c(out, "out")), lp, lm, _stream()),
+                   "ctts_vocoder_post_ragged")
+        return out
     _lib.check(_lib.load().ctts_vocoder_post(_p(_f32c(x, "x")), B, T, Cc, int(k), _p(_f32c(w, "w")), _p(_f32c(bias, "bias")), float(slope),
                                              _p(_f32c(out, "out")), _stream()), "ctts_vocoder_post")
     return out

@@ -10,7 +10,15 @@ The mel may be the transposed view of the acoustic model's channel-last [B, T, 8
 no copy.  Per forward: 1 + num_upsamples + 6 x num_upsamples x num_kernels + 1 launches (78 for V1), every leaky_relu, residual add,
 `xs += resblock(x)` and `/ num_kernels` fused into a convolution's load or epilogue.  Arithmetic: kernels.BF16_SPLIT (CTTS_X6=0 = exact
 fp32 MFMA; default = the exact three-way bf16 split).  The folded, packed (and split) weights are cached and rebuilt when a parameter
-changes (load_state_dict, remove_weight_norm, .to(), in-place edits: version counters + kernels.WEIGHTS_EPOCH)."""
+changes (load_state_dict, remove_weight_norm, .to(), in-place edits: version counters + kernels.WEIGHTS_EPOCH).
+
+`forward(mel, lens)` is the length-aware form (include/ctts.h, HiFi-GAN block): `lens` holds one mel-frame count per utterance and
+utterance b is vocoded exactly as `forward(mel[b:b + 1, :, :lens[b]])` would vocode it alone, bit for bit - the padded frames are never
+read (NaN there is harmless) and the wav holds exact zeros from sample 256 lens[b] on.  lens[b] > T behaves as T; lens[b] == 0 gives an
+all-zero row (the reference raises for an empty mel: this is our own definition).  Same launches as the dense forward (tiles beyond an
+utterance's end return at once), no host read of `lens`: a captured forward may be replayed with other values in the same tensor.
+`infer_wavs` is the ragged counterpart of the reference's `vocoder_infer` (utils/model.py:74-92)."""
+import numpy as np
 import torch
 import torch.nn as nn
 from torch.nn import Conv1d, ConvTranspose1d
@@ -137,10 +145,33 @@ class Generator(nn.Module):
         return self._cache
 
     # ---- forward -----------------------------------------------------------------------------------------------------------------
-    def forward(self, x):
-        return self._forward(x)
+    def forward(self, x, lens=None):
+        return self._forward(x, lens=lens)
 
-    def _forward(self, x, stage_cb=None):
+    @staticmethod
+    def _device_lens(lens, x):
+        """`lens` of forward() -> a contiguous device int32 [B] tensor.  A device int32 tensor goes in as it is (the kernels clamp it to
+        [0, T]); a device int64 tensor (the acoustic model's mel_lens) is clamped and narrowed on the device, no sync; a list or a CPU
+        tensor is copied to the device once.  Raises CttsError for a wrong shape or a non-integer dtype, before any launch."""
+        B, T = x.shape[0], x.shape[2]
+        if not torch.is_tensor(lens):
+            try:
+                lens = torch.as_tensor(lens)
+            except Exception as e:
+                raise _lib.CttsError(f"hifigan Generator: lens must be a tensor or a list of integers ({e})") from None
+        if lens.dtype not in (torch.int32, torch.int64):
+            raise _lib.CttsError(f"hifigan Generator: lens must be int32 or int64, got {lens.dtype}")
+        if tuple(lens.shape) != (B,):
+            raise _lib.CttsError(f"hifigan Generator: lens must have shape ({B},) for a mel {tuple(x.shape)}, got {tuple(lens.shape)}")
+        if lens.device != x.device:
+            if lens.is_cuda:
+                raise _lib.CttsError(f"hifigan Generator: lens is on {lens.device}, the mel on {x.device}")
+            lens = lens.to(x.device)
+        if lens.dtype == torch.int64:
+            lens = lens.clamp(0, T).to(torch.int32)
+        return lens.contiguous()
+
+    def _forward(self, x, stage_cb=None, lens=None):
         """forward; stage_cb(name) after conv_pre, each upsampling stage and conv_post (tools/bench_vocoder.py's per-stage events)"""
         if not x.is_cuda:
             raise _lib.CttsError("hifigan Generator: the mel must be a device (HIP) tensor - there is no CPU path")
@@ -148,11 +179,14 @@ class Generator(nn.Module):
             raise _lib.CttsError(f"hifigan Generator: expected mel [B, 80, T], got {tuple(x.shape)}")
         split = K.BF16_SPLIT
         with torch.no_grad():
+            if lens is not None:
+                lens = self._device_lens(lens, x)
+            s = 1                                              # rows per mel frame of the current signal (the kernels' len_mul)
             pre, ups, rbs, post = self._packed(split)
             xt = x.float().transpose(1, 2)                     # [B, T, 80] channel-last view (the model's own mel layout)
             c0 = self.h.upsample_initial_channel
             w, wp, b = pre
-            hcur = K.vocoder_conv(xt, w, wp, 80, c0, 7, 1, bias=b, bf16_split=split)                           # models.py:146
+            hcur = K.vocoder_conv(xt, w, wp, 80, c0, 7, 1, bias=b, bf16_split=split, lens=lens, len_mul=s)     # models.py:146
             if stage_cb:
                 stage_cb("conv_pre")
             nk = self.num_kernels
@@ -161,7 +195,8 @@ class Generator(nn.Module):
                 cin, cout = c0 // (2 ** i), c0 // (2 ** (i + 1))
                 w, wp, b = ups[i]
                 hcur = K.vocoder_conv(hcur, w, wp, cin, cout, kup, 1, transposed_u=u, slope=LRELU_SLOPE, bias=b,   # models.py:148-149
-                                      bf16_split=split)
+                                      bf16_split=split, lens=lens, len_mul=s)
+                s *= u
                 xs = torch.empty_like(hcur)
                 for j in range(nk):                                                                            # models.py:150-158
                     rb = self.resblocks[i * nk + j]
@@ -169,19 +204,34 @@ class Generator(nn.Module):
                     cur = hcur
                     for l, d in enumerate(rb.dilation):                                                         # models.py:96-104
                         (w1, wp1, b1), (w2, wp2, b2) = rbs[i * nk + j][l]
-                        t = K.vocoder_conv(cur, w1, wp1, cout, cout, k, d, slope=LRELU_SLOPE, bias=b1, bf16_split=split)
+                        t = K.vocoder_conv(cur, w1, wp1, cout, cout, k, d, slope=LRELU_SLOPE, bias=b1, bf16_split=split,
+                                           lens=lens, len_mul=s)
                         if l < len(rb.dilation) - 1:
-                            cur = K.vocoder_conv(t, w2, wp2, cout, cout, k, 1, slope=LRELU_SLOPE, bias=b2, R=cur, bf16_split=split)
+                            cur = K.vocoder_conv(t, w2, wp2, cout, cout, k, 1, slope=LRELU_SLOPE, bias=b2, R=cur, bf16_split=split,
+                                                 lens=lens, len_mul=s)
                         else:             # xs = resblock_0(x); xs += resblock_j(x); x = xs / num_kernels - in the epilogue
                             last = j == nk - 1
                             K.vocoder_conv(t, w2, wp2, cout, cout, k, 1, slope=LRELU_SLOPE, bias=b2, R=cur, out=xs,
                                            alpha=1.0 / nk if last else 1.0, beta=0.0 if j == 0 else (1.0 / nk if last else 1.0),
-                                           bf16_split=split)
+                                           bf16_split=split, lens=lens, len_mul=s)
                 hcur = xs
                 if stage_cb:
                     stage_cb(f"stage{i}")
             wpost, bpost = post
-            wav = K.vocoder_post(hcur, wpost, bpost, POST_SLOPE)                                              # models.py:161-163
+            wav = K.vocoder_post(hcur, wpost, bpost, POST_SLOPE, lens=lens, len_mul=s)                       # models.py:161-163
             if stage_cb:
                 stage_cb("conv_post")
             return wav
+
+
+def infer_wavs(vocoder, mels, mel_lens, max_wav_value=32768.0):
+    """The ragged counterpart of the reference's `vocoder_infer` (utils/model.py:74-92) with its result contract: mels [B, 80, T] on the
+    device (the transposed view of the acoustic model's [B, T, 80] output is fine), mel_lens one frame count per utterance (what
+    `Generator.forward` takes as `lens`) -> a list of B int16 numpy arrays, `(wav * max_wav_value).astype("int16")` on the host, the
+    b-th 256 x min(mel_lens[b], T) samples long (the generator's own hop: the product of its upsample_rates).  Unlike the reference,
+    each array is the audio of its utterance vocoded alone: it does not depend on the batch's padding or on the other utterances."""
+    wavs = vocoder(mels, lens=mel_lens).squeeze(1)
+    hop = wavs.shape[1] // mels.shape[2]
+    lens = mel_lens.tolist() if torch.is_tensor(mel_lens) else [int(v) for v in mel_lens]
+    wavs = (wavs.cpu().numpy() * max_wav_value).astype("int16")
+    return [wavs[i][: hop * max(0, min(int(n), mels.shape[2]))] for i, n in enumerate(lens)]

@@ -544,6 +544,17 @@ int ctts_mel_l1_bwd(const float* p1, const float* p2, const float* tgt, const fl
  *     within one fp32 rounding); 0: exact fp32 MFMA.  Bit-reproducible (no atomics).
  * ctts_vocoder_post: out[b, t] = tanh(bias[0] + sum_{tap < k, c} leaky_relu(x[b, t + tap - (k - 1) / 2, c], slope) w[tap][c]),
  *   x [B, T, C] dense, out [B, 1, T] - conv_post with its leaky_relu (default slope 0.01) and tanh (models.py:161-163); fp32 VALU.
+ * Length-aware (ragged) batches: `lens` (device int32 [B], one mel-frame count per utterance; NULL = dense, every utterance T rows)
+ *   and `len_mul` >= 1 (the layer's input rows per mel frame: 1 up to the first upsampler, then the running product of the rates).
+ *   Utterance b's input then has Tb = min(max(lens[b], 0) len_mul, T) rows and the layer computes exactly what a B = 1 call on
+ *   x[b, :Tb] computes, bit for bit: rows at or beyond Tb read as zero for every tap, R and `beta * out` are read for valid output
+ *   rows only, the transposed conv's row range and phase scatter end at Tb (its first row does not depend on the length, so the
+ *   128-row tiles stay anchored at row 0 of each utterance).  Output rows at or beyond Tb (Tb u) are NOT written by ctts_vocoder_conv
+ *   (nothing reads them); ctts_vocoder_post_ragged writes exact zeros there.  The content of x[b, Tb:] is never read (NaN / Inf there
+ *   is harmless), lens[b] > T / len_mul behaves as T (clamped in the kernel), lens[b] <= 0 is an empty utterance: nothing is written
+ *   by the conv, an all-zero row by the post kernel (our own definition: the reference raises for an empty mel).  The launch grid is
+ *   sized by the padded T (no host read of lens, no sync; a tile at or beyond its utterance's end returns before it stages anything),
+ *   so a captured graph may be replayed with other values in the same lens buffer.  Still one launch per layer and no atomics.
  * Descriptors must be zero-initialised (fields added later default to 0). */
 typedef struct ctts_vconv_desc {
   const float* x;
@@ -557,10 +568,13 @@ typedef struct ctts_vconv_desc {
   float* out;
   float alpha, beta;
   int32_t bf16_split;
+  const int32_t* lens; int32_t len_mul;
 } ctts_vconv_desc;
 int ctts_vocoder_conv(const ctts_vconv_desc* d, void* stream);
 int ctts_vocoder_post(const float* x, int B, int T, int C, int k, const float* w, const float* bias, float slope, float* out,
                       void* stream);
+int ctts_vocoder_post_ragged(const float* x, int B, int T, int C, int k, const float* w, const float* bias, float slope, float* out,
+                             const int32_t* lens, int len_mul, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Fastformer additive attention (block_type "fastformer"; reference model/transformers/fastformer.py FastAttention).  Rows (b, t) run

@@ -5,7 +5,16 @@ the vocoder) and one 870-frame utterance (LJSpeech's longest, synthesize.py --mo
 audio-seconds per second, algorithmic TFLOP/s and its fraction of 416.7 TF (the bf16 pipe / 6), per-stage ms, max-abs difference.
 
     python tools/bench_vocoder.py [--steps 20] [--warmup 5] [--out profiles/vocoder_bench.json] [--once]
---once runs a single native forward of the canonical batch and exits (for a kernel-trace profile of one forward)."""
+--once runs a single native forward of the canonical batch and exits (for a kernel-trace profile of one forward).
+
+    python tools/bench_vocoder.py --ragged [--repeats 3] [--parent parent.json] [--out profiles/vocoder_ragged_bench.json]
+--ragged measures the length-aware forward (Generator.forward(mel, lens)) instead, V1 at the canonical lengths: (a) the dense
+[16, 80, 1024] forward, (c) the same batch with lens, (d) the sum of 16 native B = 1 calls on the unpadded mels, and the dense
+B = 1 x 870 forward, and the same batch with every length 0 (each of the 78 grids dispatched, every workgroup returning at once: what
+the skipped tiles of a ragged forward still cost, scaled by their share); each the warm median over --steps, repeated --repeats times (spread = the largest gap between repeats of a case).
+--dense-only keeps to the cases that need no `lens` (so the same tool runs on a checkout that predates it); --parent FILE embeds such a
+run's figures as (b).  Also printed: the share of the conv workgroups (128-row tiles x column blocks, summed over layers) that a
+ragged forward does not skip."""
 import argparse
 import json
 import os
@@ -69,18 +78,95 @@ def timed(fn, steps, warmup, stages):
     return statistics.median(tot), {k: round(statistics.median(v), 3) for k, v in per.items()}, out
 
 
+def live_workgroup_share(h, lens, T):
+    """(not skipped, launched) workgroups of the generator's conv layers for a batch of `lens` padded to T: csrc/vocoder.hip's grid is
+    ceil(Mrows / 128) row tiles x ceil(N / BN) column blocks per utterance, and a tile at or beyond its utterance's rows returns"""
+    def blocks(n):
+        bn = 128 if n % 128 == 0 else (64 if n % 64 == 0 else 32)
+        return -(-n // bn)
+    layers = [(1, 0, blocks(h["upsample_initial_channel"]))]          # (rows per frame, extra rows of the polyphase range, blocks)
+    s, c = 1, h["upsample_initial_channel"]
+    for u, k in zip(h["upsample_rates"], h["upsample_kernel_sizes"]):
+        pad = (k - u) // 2
+        c //= 2
+        layers.append((s, (pad + u - 1) // u - pad // u, blocks(u * c)))
+        s *= u
+        layers += [(s, 0, blocks(c))] * (6 * len(h["resblock_kernel_sizes"]))
+    live = sum(-(-(n * s + e) // 128) * nb for s, e, nb in layers for n in lens if n > 0)
+    return live, sum(-(-(T * s + e) // 128) * nb * len(lens) for s, e, nb in layers)
+
+
+def ragged_main(a, dev, g, mel_lens):
+    gen = torch.Generator().manual_seed(0)
+    mel = (torch.randn(16, 1024, 80, generator=gen) * 2 - 5).to(dev)
+    single = (torch.randn(1, 870, 80, generator=gen) * 2 - 5).to(dev)
+    view, sview = mel.transpose(1, 2), single.transpose(1, 2)
+    lens = torch.tensor(mel_lens, dtype=torch.int32, device=dev)
+    alone = [view[b:b + 1, :, :n] for b, n in enumerate(mel_lens)]
+    cases = {"a_dense_B16_T1024": lambda cb: g._forward(view), "dense_single_T870": lambda cb: g._forward(sview)}
+    if not a.dense_only:
+        cases["c_ragged_B16_T1024"] = lambda cb: g._forward(view, lens=lens)
+        cases["d_sum_of_16_single_calls"] = lambda cb: [g._forward(m) for m in alone][-1]
+        empty = torch.zeros_like(lens)
+        cases["all_empty_B16_T1024"] = lambda cb: g._forward(view, lens=empty)
+    res = {"tool": "tools/bench_vocoder.py --ragged" + (" --dense-only" if a.dense_only else ""),
+           "network": "HiFi-GAN V1 (hifigan/config.json), folded weights",
+           "arithmetic": "split (exact 3-way bf16, 6 MFMA terms)" if K.BF16_SPLIT else "fp32 MFMA",
+           "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats,
+           "mel_lens": mel_lens, "valid_frames": sum(mel_lens), "padded_frames": 16 * 1024, "cases": {}}
+    runs = {k: [] for k in cases}
+    with torch.no_grad():
+        for _ in range(a.repeats):                       # interleaved: a drift of the box shows up as spread, not as a difference
+            for k, fn in cases.items():
+                runs[k].append(timed(fn, a.steps, a.warmup, False)[0])
+    for k, v in runs.items():
+        res["cases"][k] = {"ms": round(statistics.median(v), 3), "repeats_ms": [round(x, 3) for x in v], "spread_ms": round(max(v) - min(v), 3)}
+    if a.parent:
+        with open(a.parent) as f:
+            par = json.loads(f.readline())
+        res["cases"]["b_parent_dense_B16_T1024"] = par["cases"]["a_dense_B16_T1024"]
+        res["cases"]["parent_dense_single_T870"] = par["cases"]["dense_single_T870"]
+    if not a.dense_only:
+        live, total = live_workgroup_share(V1, mel_lens, 1024)
+        ms = {k: v["ms"] for k, v in res["cases"].items()}
+        res["frame_share"] = round(sum(mel_lens) / (16 * 1024), 4)
+        res["live_workgroup_share"] = round(live / total, 4)
+        res["ragged_over_dense"] = round(ms["c_ragged_B16_T1024"] / ms["a_dense_B16_T1024"], 4)
+        res["skipped_workgroups_ms_estimate"] = round((1 - live / total) * ms["all_empty_B16_T1024"], 3)
+        res["ragged_over_sum_of_singles"] = round(ms["c_ragged_B16_T1024"] / ms["d_sum_of_16_single_calls"], 4)
+        with torch.no_grad():                            # per stage (events between the stages, one more pass): where the ratio is lost
+            st_a = timed(lambda cb: g._forward(view, cb), a.steps, a.warmup, True)[1]
+            st_c = timed(lambda cb: g._forward(view, cb, lens=lens), a.steps, a.warmup, True)[1]
+        res["stage_ms"] = {k: {"dense": st_a[k], "ragged": st_c[k], "ratio": round(st_c[k] / st_a[k], 3)} for k in st_a}
+        with torch.no_grad():                            # what the tool times is what the tests hold: bit-equal to the B = 1 calls
+            wav = g(view, lens=lens)
+            res["bit_equal_to_single_calls"] = all(torch.equal(wav[b, 0, :HOP * n], g(alone[b])[0, 0]) for b, n in enumerate(mel_lens))
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--ragged", action="store_true")
+    ap.add_argument("--dense-only", action="store_true")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--parent", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = v1_generator(dev)
     W = R.fold_state_dict(g.state_dict(), dtype=torch.float32, device=dev)
     batch = make_batch(seed=1234)
     mel_lens = [int(v) for v in batch["mel_lens"]]
+    if a.ragged:
+        return ragged_main(a, dev, g, mel_lens)
     gen = torch.Generator().manual_seed(0)
     shapes = {"canonical_B16_T1024": torch.randn(16, 1024, 80, generator=gen) * 2 - 5,
               "single_T870": torch.randn(1, 870, 80, generator=gen) * 2 - 5}
