@@ -65,6 +65,23 @@ class VconvDesc(C.Structure):
     ]
 
 
+class VconvHDesc(C.Structure):
+    """ctts_vconv_h_desc of include/ctts.h (the fp16 mode's descriptor; ctypes zero-initialises it)"""
+    _fields_ = [
+        ("x", _vp), ("sxb", _i64), ("sxt", _i64), ("sxc", _i64),
+        ("x_f32", _i32),
+        ("B", _i32), ("T", _i32), ("Cin", _i32), ("Cout", _i32), ("k", _i32), ("dil", _i32),
+        ("transposed_u", _i32),
+        ("act_in", _i32), ("slope", _f32),
+        ("w", _vp),
+        ("bias", _vp),
+        ("R", _vp),
+        ("out", _vp),
+        ("alpha", _f32), ("beta", _f32),
+        ("lens", _vp), ("len_mul", _i32),
+    ]
+
+
 class PsumTask(C.Structure):
     """ctts_psum_task of include/ctts.h"""
     _fields_ = [("src", _vp), ("dst", _vp), ("n", _i64), ("stride", _i64), ("count", _i32), ("alpha", _f32)]
@@ -162,6 +179,8 @@ _SIGNATURES = {
     "ctts_vocoder_conv": [C.POINTER(VconvDesc), _vp],
     "ctts_vocoder_post": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _f32, _vp, _vp],
     "ctts_vocoder_post_ragged": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _f32, _vp, _vp, C.c_int, _vp],
+    "ctts_vocoder_conv_h": [C.POINTER(VconvHDesc), _vp],
+    "ctts_vocoder_post_h": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _f32, _vp, _vp, C.c_int, _vp],
     "ctts_fastformer_pool_fwd": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, _vp],
     "ctts_fastformer_pool_bwd": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, _vp],
     "ctts_fastformer_bcast": [_vp, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp],

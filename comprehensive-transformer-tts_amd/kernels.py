@@ -1327,6 +1327,90 @@ def vocoder_post(x, w, bias, slope=0.01, out=None, lens=None, len_mul=1):
     return out
 
 
+# ---- HiFi-GAN vocoder, fp16 mode (csrc/vocoder_h.hip) ---------------------------------------------------------------------------
+FP16_MAX = 65504.0
+
+
+def vocoder_pack_weight_h(weight, transposed_u=0):
+    """Folded conv weight -> the packed fp16 operand of ctts_vocoder_conv_h [roundup(N, 128), taps * roundup(Cin, 32)]: the fp32 pack of
+    vocoder_pack_weight, rounded once to fp16 (round to nearest even, saturated to +-65504).  A one-time layout change of a constant."""
+    packed, _ = vocoder_pack_weight(weight, transposed_u, planes=False)
+    return packed.clamp_(-FP16_MAX, FP16_MAX).to(torch.float16).contiguous()
+
+
+def _f16c(t, name):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float16 and t.is_contiguous()):
+        raise _lib.CttsError(f"{name}: need a contiguous device float16 tensor")
+    return t
+
+
+def vocoder_conv_h(x, w, Cin, Cout, k, dil=1, transposed_u=0, slope=None, bias=None, R=None, out=None, alpha=1.0, beta=0.0,
+                   lens=None, len_mul=1):
+    """One generator layer in the fp16 mode (include/ctts.h ctts_vocoder_conv_h).  x: [B, T, Cin] with any strides, float32 (the mel:
+    rounded to fp16 when staged) or float16; w from vocoder_pack_weight_h; bias fp32; R / out fp16 [B, T_out, Cout] dense.
+    -> out = fp16(beta * out + alpha * (conv + bias + R)), saturated to +-65504.  lens / len_mul as vocoder_conv."""
+    if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.float16) or x.dim() != 3:
+        raise _lib.CttsError(f"vocoder_conv_h: x must be a 3-D float32 or float16 tensor [B, T, Cin], got "
+                             f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    if not x.is_cuda:
+        raise _lib.CttsError("vocoder_conv_h: x must be a device (HIP) tensor")
+    B, T, cin = x.shape
+    if cin != Cin:
+        raise _lib.CttsError(f"vocoder_conv_h: x has {cin} channels, the layer {Cin}")
+    Tout = T * transposed_u if transposed_u else T
+    if out is None:
+        if beta != 0.0:
+            raise _lib.CttsError("vocoder_conv_h: beta != 0 needs `out`")
+        out = torch.empty(B, Tout, Cout, dtype=torch.float16, device=x.device)
+    elif tuple(out.shape) != (B, Tout, Cout):
+        raise _lib.CttsError(f"vocoder_conv_h: out has shape {tuple(out.shape)}, expected {(B, Tout, Cout)}")
+    if R is not None and tuple(R.shape) != (B, Tout, Cout):
+        raise _lib.CttsError(f"vocoder_conv_h: R has shape {tuple(R.shape)}, expected {(B, Tout, Cout)}")
+    N, taps = (transposed_u * Cout, k // transposed_u) if transposed_u else (Cout, k)
+    wshape = (-(-N // 128) * 128, taps * (-(-Cin // 32) * 32))
+    if tuple(_f16c(w, "vocoder_conv_h weight").shape) != wshape:
+        raise _lib.CttsError(f"vocoder_conv_h: packed weight {tuple(w.shape)} does not match the layer (expected {wshape})")
+    for t, name in ((w, "weight"), (bias, "bias"), (R, "R"), (out, "out")):
+        if t is not None and t.device != x.device:
+            raise _lib.CttsError(f"vocoder_conv_h: {name} is on {t.device}, x on {x.device}")
+    d = _lib.VconvHDesc()
+    d.x = _p(x)
+    d.x_f32 = 1 if x.dtype == torch.float32 else 0
+    d.sxb, d.sxt, d.sxc = (int(s) for s in x.stride())
+    d.B, d.T, d.Cin, d.Cout, d.k, d.dil = B, T, int(Cin), int(Cout), int(k), int(dil)
+    d.transposed_u = int(transposed_u)
+    d.act_in = 0 if slope is None else 1
+    d.slope = 0.0 if slope is None else float(slope)
+    d.w = _p(w)
+    d.bias = _p(None if bias is None else _f32c(bias, "bias"))
+    d.R = _p(None if R is None else _f16c(R, "vocoder_conv_h R"))
+    d.out = _p(_f16c(out, "vocoder_conv_h out"))
+    d.alpha, d.beta = float(alpha), float(beta)
+    d.lens, d.len_mul = _vocoder_lens(lens, len_mul, B, "vocoder_conv_h")
+    _lib.check(_lib.load().ctts_vocoder_conv_h(C.byref(d), _stream()), "ctts_vocoder_conv_h")
+    return out
+
+
+def vocoder_post_h(x, w, bias, slope=0.01, out=None, lens=None, len_mul=1):
+    """conv_post + tanh on fp16 activations (include/ctts.h ctts_vocoder_post_h): x fp16 [B, T, C] dense, w fp32 [k, C], bias fp32 [1]
+    -> fp32 [B, 1, T]; lens (device int32 [B]) / len_mul: exact zeros from row lens[b] len_mul on."""
+    if not torch.is_tensor(x) or x.dim() != 3:
+        raise _lib.CttsError("vocoder_post_h: x must be a 3-D float16 tensor [B, T, C]")
+    _f16c(x, "vocoder_post_h x")
+    B, T, Cc = x.shape
+    if w.dim() != 2 or w.shape[1] != Cc or w.shape[0] % 2 == 0:
+        raise _lib.CttsError(f"vocoder_post_h: w must be [k, {Cc}] with k odd, got {tuple(w.shape)}")
+    k = w.shape[0]
+    if out is None:
+        out = torch.empty(B, 1, T, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, 1, T):
+        raise _lib.CttsError(f"vocoder_post_h: out has shape {tuple(out.shape)}, expected {(B, 1, T)}")
+    lp, lm = _vocoder_lens(lens, len_mul, B, "vocoder_post_h")
+    _lib.check(_lib.load().ctts_vocoder_post_h(_p(x), B, T, Cc, int(k), _p(_f32c(w, "w")), _p(_f32c(bias, "bias")), float(slope),
+                                               _p(_f32c(out, "out")), lp, lm, _stream()), "ctts_vocoder_post_h")
+    return out
+
+
 # ---- Fastformer additive attention (csrc/fastformer.hip) ----------------------------------------------------------------------
 def _rows_ld(t, C, name):
     """(row stride) of a [B*T, C]-shaped fp32 operand that may be a column slice of a wider matrix (unit column stride)"""

@@ -17,7 +17,18 @@ utterance b is vocoded exactly as `forward(mel[b:b + 1, :, :lens[b]])` would voc
 read (NaN there is harmless) and the wav holds exact zeros from sample 256 lens[b] on.  lens[b] > T behaves as T; lens[b] == 0 gives an
 all-zero row (the reference raises for an empty mel: this is our own definition).  Same launches as the dense forward (tiles beyond an
 utterance's end return at once), no host read of `lens`: a captured forward may be replayed with other values in the same tensor.
-`infer_wavs` is the ragged counterpart of the reference's `vocoder_infer` (utils/model.py:74-92)."""
+`infer_wavs` is the ragged counterpart of the reference's `vocoder_infer` (utils/model.py:74-92).
+
+The module call `g(mel, lens=None, precision=None)`: "fp32" (the default) is the path above; "fp16" is the half-precision inference mode on the kernels of
+csrc/vocoder_h.hip (include/ctts.h, "fp16 mode": fp16 weights and activations, one v_mfma_f32_32x32x16_f16 term per product, fp32
+accumulation, epilogue and conv_post; the wav is fp32 in both modes).  `precision=None` means `self.default_precision`, which the
+constructor takes from the environment variable CTTS_VOCODER_PRECISION (unset / "fp32" / "fp16") - the switch of the zero-edit drop-in
+route, whose `vocoder_infer` calls `vocoder(mels)`.  Each mode has its own packed-weight cache under the same invalidation rules, so the
+two can be mixed on one generator in any order.  `forward(mel, lens)` itself keeps the two-argument signature its callers and tests
+know and runs the precision of the call in progress (`precision` of `g(...)`, else default_precision); `infer_wavs` keeps its
+signature too and follows the generator's default_precision.  `Generator.half()` is not the switch: it converts the parameters as on any nn.Module."""
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -29,6 +40,14 @@ from . import kernels as K
 
 LRELU_SLOPE = 0.1          # models.py:7
 POST_SLOPE = 0.01          # F.leaky_relu's default, models.py:161
+PRECISIONS = ("fp32", "fp16")
+PRECISION_ENV = "CTTS_VOCODER_PRECISION"
+
+
+def _check_precision(p, what):
+    if p not in PRECISIONS:
+        raise ValueError(f"{what}: precision must be one of {PRECISIONS}, got {p!r}")
+    return p
 
 
 class AttrDict(dict):
@@ -112,6 +131,10 @@ class Generator(nn.Module):
         self.conv_post = _weight_norm(Conv1d(ch, 1, 7, 1, padding=3))
         self._cache_key = None
         self._cache = None
+        self._cache_h_key = None                              # the fp16 mode's own pack: neither mode rebuilds or reads the other's
+        self._cache_h = None
+        self._call_precision = None                           # set by __call__(..., precision=) for the duration of that call
+        self.default_precision = _check_precision(os.environ.get(PRECISION_ENV) or "fp32", PRECISION_ENV)
 
     def remove_weight_norm(self):
         for m in self.ups:
@@ -125,14 +148,11 @@ class Generator(nn.Module):
     def _key(self, split):
         return (split, K.WEIGHTS_EPOCH[0], tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in self.parameters()))
 
-    def _packed(self, split):
-        key = self._key(split)
-        if key == self._cache_key:
-            return self._cache
-
+    def _build_pack(self, pack):
+        """(pre, ups, resblocks, post) with every conv as pack(folded weight, transposed_u) + (fp32 bias,); conv_post's weight as fp32
+        [k, C].  The one traversal both modes' caches are built by."""
         def conv(m, u=0):
-            w, wp = K.vocoder_pack_weight(_folded_weight(m), transposed_u=u, planes=split)
-            return (w, wp, m.bias.detach().float().contiguous())
+            return tuple(pack(_folded_weight(m), u)) + (m.bias.detach().float().contiguous(),)
 
         with torch.no_grad():
             pre = conv(self.conv_pre)
@@ -140,13 +160,40 @@ class Generator(nn.Module):
             rbs = [[(conv(c1), conv(c2)) for c1, c2 in zip(rb.convs1, rb.convs2)] for rb in self.resblocks]
             wpost = _folded_weight(self.conv_post)[0].detach().float().t().contiguous()        # [k, C]
             post = (wpost, self.conv_post.bias.detach().float().contiguous())
-        self._cache = (pre, ups, rbs, post)
-        self._cache_key = key
+        return (pre, ups, rbs, post)
+
+    def _packed(self, split):
+        key = self._key(split)
+        if key != self._cache_key:
+            self._cache = self._build_pack(lambda w, u: K.vocoder_pack_weight(w, transposed_u=u, planes=split))
+            self._cache_key = key
         return self._cache
 
+    def _packed_h(self):
+        """the fp16 mode's weights: folded in fp32, rounded once to fp16 and packed (kernels.vocoder_pack_weight_h); biases and
+        conv_post's weight stay fp32.  Its own cache slot under the same key rule: neither mode rebuilds or reads the other's."""
+        key = self._key("fp16")
+        if key != self._cache_h_key:
+            self._cache_h = self._build_pack(lambda w, u: (K.vocoder_pack_weight_h(w, transposed_u=u),))
+            self._cache_h_key = key
+        return self._cache_h
+
     # ---- forward -----------------------------------------------------------------------------------------------------------------
+    def __call__(self, x, lens=None, precision=None):
+        """the module call with the per-call `precision` ("fp32" / "fp16"; None = self.default_precision): nn.Module's own call (hooks
+        included) around forward(x, lens), which reads the precision of the call in progress.  A bad value raises ValueError here.
+        forward keeps its (x, lens) signature, so the value travels on the module for the duration of the call: one generator must
+        not be called from two threads with different `precision` arguments at once (calls that leave it None are unaffected)."""
+        if precision is None:
+            return super().__call__(x, lens=lens)
+        prev, self._call_precision = self._call_precision, _check_precision(precision, "hifigan Generator")
+        try:
+            return super().__call__(x, lens=lens)
+        finally:
+            self._call_precision = prev
+
     def forward(self, x, lens=None):
-        return self._forward(x, lens=lens)
+        return self._forward(x, lens=lens, precision=self._call_precision)
 
     @staticmethod
     def _device_lens(lens, x):
@@ -171,12 +218,15 @@ class Generator(nn.Module):
             lens = lens.clamp(0, T).to(torch.int32)
         return lens.contiguous()
 
-    def _forward(self, x, stage_cb=None, lens=None):
+    def _forward(self, x, stage_cb=None, lens=None, precision=None):
         """forward; stage_cb(name) after conv_pre, each upsampling stage and conv_post (tools/bench_vocoder.py's per-stage events)"""
+        precision = _check_precision(self.default_precision if precision is None else precision, "hifigan Generator")
         if not x.is_cuda:
             raise _lib.CttsError("hifigan Generator: the mel must be a device (HIP) tensor - there is no CPU path")
         if x.dim() != 3 or x.shape[1] != 80:
             raise _lib.CttsError(f"hifigan Generator: expected mel [B, 80, T], got {tuple(x.shape)}")
+        if precision == "fp16":
+            return self._forward_h(x, stage_cb, lens)
         split = K.BF16_SPLIT
         with torch.no_grad():
             if lens is not None:
@@ -224,12 +274,58 @@ class Generator(nn.Module):
             return wav
 
 
+    def _forward_h(self, x, stage_cb, lens):
+        """the fp16 mode (include/ctts.h): the launches of _forward on ctts_vocoder_conv_h / ctts_vocoder_post_h, fp16 activations"""
+        with torch.no_grad():
+            if lens is not None:
+                lens = self._device_lens(lens, x)
+            s = 1
+            pre, ups, rbs, post = self._packed_h()
+            xt = x.float().transpose(1, 2)                     # fp32 [B, T, 80] view: rounded to fp16 when the first layer stages it
+            c0 = self.h.upsample_initial_channel
+            w, b = pre
+            hcur = K.vocoder_conv_h(xt, w, 80, c0, 7, 1, bias=b, lens=lens, len_mul=s)
+            if stage_cb:
+                stage_cb("conv_pre")
+            nk = self.num_kernels
+            for i in range(self.num_upsamples):
+                u, kup = self.h.upsample_rates[i], self.h.upsample_kernel_sizes[i]
+                cin, cout = c0 // (2 ** i), c0 // (2 ** (i + 1))
+                w, b = ups[i]
+                hcur = K.vocoder_conv_h(hcur, w, cin, cout, kup, 1, transposed_u=u, slope=LRELU_SLOPE, bias=b, lens=lens, len_mul=s)
+                s *= u
+                xs = torch.empty_like(hcur)
+                for j in range(nk):
+                    rb = self.resblocks[i * nk + j]
+                    k = rb.kernel_size
+                    cur = hcur
+                    for l, d in enumerate(rb.dilation):
+                        (w1, b1), (w2, b2) = rbs[i * nk + j][l]
+                        t = K.vocoder_conv_h(cur, w1, cout, cout, k, d, slope=LRELU_SLOPE, bias=b1, lens=lens, len_mul=s)
+                        if l < len(rb.dilation) - 1:
+                            cur = K.vocoder_conv_h(t, w2, cout, cout, k, 1, slope=LRELU_SLOPE, bias=b2, R=cur, lens=lens, len_mul=s)
+                        else:
+                            last = j == nk - 1
+                            K.vocoder_conv_h(t, w2, cout, cout, k, 1, slope=LRELU_SLOPE, bias=b2, R=cur, out=xs,
+                                             alpha=1.0 / nk if last else 1.0, beta=0.0 if j == 0 else (1.0 / nk if last else 1.0),
+                                             lens=lens, len_mul=s)
+                hcur = xs
+                if stage_cb:
+                    stage_cb(f"stage{i}")
+            wpost, bpost = post
+            wav = K.vocoder_post_h(hcur, wpost, bpost, POST_SLOPE, lens=lens, len_mul=s)
+            if stage_cb:
+                stage_cb("conv_post")
+            return wav
+
+
 def infer_wavs(vocoder, mels, mel_lens, max_wav_value=32768.0):
     """The ragged counterpart of the reference's `vocoder_infer` (utils/model.py:74-92) with its result contract: mels [B, 80, T] on the
     device (the transposed view of the acoustic model's [B, T, 80] output is fine), mel_lens one frame count per utterance (what
     `Generator.forward` takes as `lens`) -> a list of B int16 numpy arrays, `(wav * max_wav_value).astype("int16")` on the host, the
     b-th 256 x min(mel_lens[b], T) samples long (the generator's own hop: the product of its upsample_rates).  Unlike the reference,
-    each array is the audio of its utterance vocoded alone: it does not depend on the batch's padding or on the other utterances."""
+    each array is the audio of its utterance vocoded alone: it does not depend on the batch's padding or on the other utterances.
+    The arithmetic is the generator's `default_precision` ("fp32" / "fp16": set the attribute, or CTTS_VOCODER_PRECISION)."""
     wavs = vocoder(mels, lens=mel_lens).squeeze(1)
     hop = wavs.shape[1] // mels.shape[2]
     lens = mel_lens.tolist() if torch.is_tensor(mel_lens) else [int(v) for v in mel_lens]

@@ -577,6 +577,51 @@ int ctts_vocoder_post_ragged(const float* x, int B, int T, int C, int k, const f
                              const int32_t* lens, int len_mul, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * HiFi-GAN vocoder, fp16 mode (csrc/vocoder_h.hip; vocoder.Generator called as g(mel, lens, precision="fp16")).  The same layers, shapes,
+ * weight layout (ConvTranspose1d polyphase form included), epilogue and ragged contract as ctts_vocoder_conv / ctts_vocoder_post above;
+ * what differs is the number format.  The fp32 entry points and ctts_vconv_desc are untouched by it.  Arithmetic contract:
+ *   weights     folded in fp32 as for the fp32 mode, then rounded ONCE to fp16 (round to nearest even; a value beyond +-65504 is
+ *               saturated to it) and packed [roundup(N, 128)][taps][roundup(Cin, 32)] fp16, zero padded, 16-byte aligned.  Biases stay fp32.
+ *   input       x_f32 = 1: fp32 elements read through (sxb, sxt, sxc) - the mel, whose transposed [B, T, 80] view needs no copy - and
+ *               rounded to fp16 when staged; x_f32 = 0: fp16 elements (strides in elements; dense [B, T, C] rows are read 16 bytes at a time).
+ *   activations every inter-layer tensor is fp16 [B, T, C] dense, the ResBlocks' `xs` accumulator included (nothing is kept in fp32).
+ *   operand     fp16(leaky_relu(float(x), slope)): computed in fp32, rounded once (act_in = 0: fp16(float(x))).
+ *               Saturation to +-65504 belongs to a rounding: an fp16 input that is read without one (act_in = 0, dense rows) reaches the
+ *               MFMA as it is, an inf included.  The generator never does this: every fp16-input layer has act_in = 1 and no stored
+ *               activation is inf.
+ *   products    v_mfma_f32_32x32x16_f16, fp32 accumulation over the whole K = taps x Cin in a fixed order (32-channel chunk, then tap,
+ *               then channel); no atomics, every output element is one lane's accumulator: bit-reproducible run to run, and independent
+ *               of the tile shape the launcher picks (256-row tiles for large layers, 128-row tiles otherwise).
+ *   epilogue    fp32: v = beta * float(out) + alpha * (acc + bias[co] + float(R)), R and out read from fp16 (beta == 0 never reads out),
+ *               then ONE rounding to fp16 on store, round to nearest even, saturated to +-65504: no inf is ever produced (NaN stays NaN).
+ *   conv_post   ctts_vocoder_post_h reads fp16, computes leaky_relu, the 7-tap dot product (fp32 weights) and tanh on the VALU in fp32,
+ *               writes fp32 [B, 1, T].  lens == NULL: dense; otherwise the ragged form (exact zeros from row Tb on).
+ *   subnormals  fp16 subnormal operands are NOT flushed by v_mfma_f32_32x32x16_f16 on gfx950 and subnormal results are stored as such
+ *               (the kernels run with the default fp16 denormal mode): tests/test_vocoder_half_gpu.py::test_conv_subnormal_operands
+ *               multiplies subnormal weights by subnormal-free and subnormal inputs and gets the exact products.  No per-layer scale
+ *               is applied.
+ * Ragged batches: lens / len_mul exactly as above - tiles anchored at row 0 of each utterance, the utterance's own length in T's place
+ *   everywhere, tiles beyond its end return before they stage anything, lens[b] > T behaves as T, the content of x[b, Tb:] is never read,
+ *   no host read of lens.  Descriptors must be zero-initialised. */
+typedef struct ctts_vconv_h_desc {
+  const void* x;
+  int64_t sxb, sxt, sxc;
+  int32_t x_f32;
+  int32_t B, T, Cin, Cout, k, dil;
+  int32_t transposed_u;
+  int32_t act_in; float slope;
+  const uint16_t* w;
+  const float* bias;
+  const uint16_t* R;
+  uint16_t* out;
+  float alpha, beta;
+  const int32_t* lens; int32_t len_mul;
+} ctts_vconv_h_desc;
+int ctts_vocoder_conv_h(const ctts_vconv_h_desc* d, void* stream);
+int ctts_vocoder_post_h(const uint16_t* x, int B, int T, int C, int k, const float* w, const float* bias, float slope, float* out,
+                        const int32_t* lens, int len_mul, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Fastformer additive attention (block_type "fastformer"; reference model/transformers/fastformer.py FastAttention).  Rows (b, t) run
  * over the PADDED length T (B*T rows), columns c = h*D + j for H heads of size D (C = H*D, D a power of two <= 64, C % 64 == 0,
  * C <= 1024).  Logits s [B*T, H] (row stride lds) come from the logit projections; lens int32 [B] are the valid lengths.

@@ -14,7 +14,14 @@ B = 1 x 870 forward, and the same batch with every length 0 (each of the 78 grid
 the skipped tiles of a ragged forward still cost, scaled by their share); each the warm median over --steps, repeated --repeats times (spread = the largest gap between repeats of a case).
 --dense-only keeps to the cases that need no `lens` (so the same tool runs on a checkout that predates it); --parent FILE embeds such a
 run's figures as (b).  Also printed: the share of the conv workgroups (128-row tiles x column blocks, summed over layers) that a
-ragged forward does not skip."""
+ragged forward does not skip.
+
+    python tools/bench_vocoder.py --precision fp16 [--ragged] [--repeats 3] [--out profiles/vocoder_half_bench.json]
+--precision fp16 measures the half-precision inference mode (g(mel, precision="fp16") on a Generator, csrc/vocoder_h.hip) in one run
+at both shapes: the native fp16 mode, the native fp32 mode and stock torch fp16 (the restatement's F.conv1d / F.conv_transpose1d on the
+same folded weights after .half(), MIOpen), interleaved and repeated like --ragged; with --ragged also both native modes with `lens` on
+the canonical batch.  Reported: the ratios, the per-stage ms of both native modes and the wav error (max, rms) of both half paths
+against the native fp32 output."""
 import argparse
 import json
 import os
@@ -149,6 +156,70 @@ def ragged_main(a, dev, g, mel_lens):
             f.write(line + "\n")
 
 
+def half_main(a, dev, g, mel_lens):
+    gen = torch.Generator().manual_seed(0)
+    mels = {"canonical_B16_T1024": (torch.randn(16, 1024, 80, generator=gen) * 2 - 5).to(dev),
+            "single_T870": (torch.randn(1, 870, 80, generator=gen) * 2 - 5).to(dev)}
+    if a.once:                                           # one fp16 forward of the canonical batch (for a kernel-trace profile)
+        with torch.no_grad():
+            g(mels["canonical_B16_T1024"].transpose(1, 2), precision="fp16")
+            g(mels["canonical_B16_T1024"].transpose(1, 2), precision="fp16")     # the second one runs on the cached pack
+        torch.cuda.synchronize()
+        print(json.dumps({"once": "canonical_B16_T1024", "precision": "fp16"}))
+        return
+    W16 = R.fold_state_dict(g.state_dict(), dtype=torch.float16, device=dev)
+    lens = torch.tensor(mel_lens, dtype=torch.int32, device=dev)
+    res = {"tool": "tools/bench_vocoder.py --precision fp16" + (" --ragged" if a.ragged else ""),
+           "network": "HiFi-GAN V1 (hifigan/config.json), folded weights",
+           "fp32_arithmetic": "split (exact 3-way bf16, 6 MFMA terms)" if K.BF16_SPLIT else "fp32 MFMA",
+           "fp16_arithmetic": "fp16 weights and activations, v_mfma_f32_32x32x16_f16, fp32 accumulation (include/ctts.h)",
+           "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats,
+           "shapes": {}}
+    fpf = R.flops_per_frame(V1)
+    for name, m in mels.items():
+        view = m.transpose(1, 2)
+        B, _, T = view.shape
+        half_view = view.contiguous().half()             # a dense [B, 80, T] half mel: stock torch at its best, no re-layout per call
+        cases = {"native_fp16": lambda cb: g._forward(view, precision="fp16"),
+                 "native_fp32": lambda cb: g._forward(view, precision="fp32"),
+                 "stock_torch_fp16": lambda cb: R.generator_forward(W16, V1, half_view)}
+        if a.ragged and B > 1:
+            cases["native_fp16_ragged"] = lambda cb: g._forward(view, lens=lens, precision="fp16")
+            cases["native_fp32_ragged"] = lambda cb: g._forward(view, lens=lens, precision="fp32")
+        runs = {k: [] for k in cases}
+        with torch.no_grad():
+            for _ in range(a.repeats):                   # interleaved: a drift of the box shows up as spread, not as a difference
+                for k, fn in cases.items():
+                    runs[k].append(timed(fn, a.steps, a.warmup, False)[0])
+            st16 = timed(lambda cb: g._forward(view, cb, precision="fp16"), a.steps, a.warmup, True)[1]
+            st32 = timed(lambda cb: g._forward(view, cb, precision="fp32"), a.steps, a.warmup, True)[1]
+            ref = g(view, precision="fp32").double()
+            err = {}
+            for k, out in (("native_fp16", g(view, precision="fp16")), ("stock_torch_fp16", R.generator_forward(W16, V1, half_view))):
+                e = out.double() - ref
+                err[k] = {"max": e.abs().max().item(), "rms": e.pow(2).mean().sqrt().item(), "finite": bool(torch.isfinite(out).all())}
+        flop, audio_s = fpf * B * T, B * T * HOP / SR
+        ms = {k: statistics.median(v) for k, v in runs.items()}
+        sh = {"B": B, "T": T, "tflop": round(flop / 1e12, 3), "wav_std": round(ref.std().item(), 4), "cases": {}}
+        for k, v in runs.items():
+            sh["cases"][k] = {"ms": round(ms[k], 3), "repeats_ms": [round(x, 3) for x in v], "spread_ms": round(max(v) - min(v), 3),
+                              "audio_s_per_s": round(audio_s / (ms[k] / 1e3), 1), "tflops": round(flop / ms[k] / 1e9, 1)}
+        sh["fp32_over_fp16"] = round(ms["native_fp32"] / ms["native_fp16"], 3)
+        sh["stock_fp16_over_native_fp16"] = round(ms["stock_torch_fp16"] / ms["native_fp16"], 3)
+        if "native_fp16_ragged" in ms:
+            sh["fp32_over_fp16_ragged"] = round(ms["native_fp32_ragged"] / ms["native_fp16_ragged"], 3)
+            sh["valid_frames"], sh["padded_frames"] = sum(mel_lens), B * T
+        sh["stage_ms"] = {k: {"fp16": st16[k], "fp32": st32[k], "ratio": round(st32[k] / st16[k], 3)} for k in st16}
+        sh["wav_error_vs_native_fp32"] = err
+        res["shapes"][name] = sh
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -159,12 +230,15 @@ def main():
     ap.add_argument("--dense-only", action="store_true")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--parent", default=None)
+    ap.add_argument("--precision", choices=("fp32", "fp16"), default="fp32")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = v1_generator(dev)
     W = R.fold_state_dict(g.state_dict(), dtype=torch.float32, device=dev)
     batch = make_batch(seed=1234)
     mel_lens = [int(v) for v in batch["mel_lens"]]
+    if a.precision == "fp16":
+        return half_main(a, dev, g, mel_lens)
     if a.ragged:
         return ragged_main(a, dev, g, mel_lens)
     gen = torch.Generator().manual_seed(0)
