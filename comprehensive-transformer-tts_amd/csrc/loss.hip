@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void var_loss_bwd_kernel(const VarLossArgs a) 
     const float dg = dur_at(a, i) * nonpad;
     const float ld = a.log_d[i];
     const float ex = expf(ld);
-    const float dlin = (ex - 1.f) > 0.f ? ex : 0.f;          // d clamp(exp(x) - 1, min 0) / dx
+    const float dlin = (ex - 1.f) >= 0.f ? ex : 0.f;         // d clamp(exp(x) - 1, min 0) / dx; the bound passes, as torch's clamp
     float gd = g_pd * 2.f * (ld - logf(dg + 1.f)) * nonpad + g_s * dlin;
     if (a.lam_word > 0.f) {
       const int w = wid[t];
@@ -233,7 +233,7 @@ __global__ void bin_loss_bwd_kernel(const float* __restrict__ soft, const float*
   const float k = -g[0] / out[1];
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float s = soft[i];
-    dsoft[i] = s > 1e-12f ? k * hard[i] / s : 0.f;
+    dsoft[i] = s >= 1e-12f ? k * hard[i] / s : 0.f;          // the bound passes, as torch's clamp
   }
 }
 

@@ -55,7 +55,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                     float eps, float wd, float max_norm, const float* __restrict__ state) {
   const float total = sqrtf(state[0]);
   float coef = 1.f;
-  if (max_norm > 0.f) coef = fminf(1.f, max_norm / (total + 1e-6f));        // clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1)
+  if (max_norm > 0.f) {                                                      // clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1)
+    const float c = max_norm / (total + 1e-6f);
+    coef = c > 1.f ? 1.f : c;                                                // a NaN norm stays NaN (fminf would drop it): the step is poisoned
+  }
   const float step = state[1] + 1.f;
   const float bc1 = 1.f - powf(b1, step), bc2 = 1.f - powf(b2, step);
   const float step_size = lr[0] / bc1, inv_sqrt_bc2 = rsqrtf(bc2);

@@ -365,6 +365,8 @@ int ctts_embedding_bwd(const int64_t* ids, const float* dy, float* dweight, int6
 /* ---------------------------------------------------------------------------------------
  * Unsupervised duration modelling.
  * ctts_neg_sqdist: AlignmentEncoder scores out[b,t,s] = -temp * sum_c (q[b,t,c]-k[b,s,c])^2  (model/modules.py:1199-1200), channel-last.
+ *   q [B,Tq,C], k [B,Tk,C], out [B,Tq,Tk]; every element of out is written.  C <= 255 (a 64-key tile of C+1 floats per key lives in
+ *   LDS); a larger C is refused ("C too large for the LDS tile").
  * ctts_mas: monotonic alignment search, width 1 (model/modules.py:36-75 mas_width1/b_mas; called from :863-872).
  *   attn [B,Tq,Tk] soft attention (probabilities), in_lens/out_lens [B] valid text / mel lengths;
  *   opt [B,Tq,Tk] <- hard 0/1 alignment, dur [B,Tk] <- frames per phoneme (attn_hard.sum(2)), back [B,Tq,Tk] scratch bytes. */
@@ -477,8 +479,16 @@ int ctts_relmha_bwd(const float* qu, const float* qv, const float* kv, const flo
  *   Scratch kept for the backward: partials [B,16], wsum [B,2,Ts+1], denoms [4].  Deterministic (no atomics, no memset nodes:
  *   torch's multi-block reduction mis-replays its semaphore memset inside a hipGraph on this stack).
  *   bwd: g8 = upstream gradient of every term; writes d_log_d, d_e [B,Ts], d_cwt [B,Tm,11], d_f0m, d_f0s [B].
+ *   Boundaries follow torch's autograd: the linear duration clamp(exp(log_d) - 1, min 0) passes its gradient AT the bound
+ *   (exp(log_d) - 1 >= 0, so log_d == 0 - every padded token of the model - has slope 1 in the word and sentence terms), |x| has
+ *   slope 0 at x == 0 (cwt l1, f0 statistics, energy).  A batch without any counted word (no silence token, or no word with a positive
+ *   target) gives wdur = 0/0 = NaN, as the reference does; its backward then adds NO word-term contribution (no token belongs to a
+ *   counted word), so all five gradients stay finite and equal those of lambda_word = 0 - without a silence token that is also
+ *   what autograd gives; with silences but only zero-target words autograd would hand NaN to those words' tokens, here the NaN value
+ *   is the signal.
  * ctts_bin_loss_*: BinLoss (loss.py:380-386) = -sum(log(clamp(soft,1e-12)) * hard) / sum(hard) over n elements; partials [1024],
- *   out2 = {loss, sum hard}. */
+ *   out2 = {loss, sum hard}.  The bound is the float32 nearest to 1e-12; bwd passes the gradient at soft >= bound (the bound included,
+ *   as torch's clamp) and writes 0 below it. */
 int ctts_var_loss_fwd(const float* log_d, const void* dur, int dur_is_float, const int64_t* texts, const uint8_t* src_pad, const float* cwt,
                       const float* cwt_spec, const float* uv, const uint8_t* mel_pad, const float* f0m_p, const float* f0m_t,
                       const float* f0s_p, const float* f0s_t, const float* e_pred, const float* e_tgt, int B, int Ts, int Tm,
@@ -508,7 +518,10 @@ int ctts_masked_loss_bwd(const float* pred, const float* target, const float* we
  * p, g, m, v: n floats each, 16-byte aligned.  lr: device scalar.  state: CTTS_ADAM_STATE_FLOATS device floats {sum of squares of this
  * call (output), step count t-1 (incremented here), total norm of this call (output), CTTS_ADAM_PARTIALS per-block partial sums
  * (scratch)} - all device resident so that the launches replay inside a hipGraph.  The norm is reduced in a FIXED order (no atomics):
- * data-parallel replicas with bit-identical gradients stay bit-identical. */
+ * data-parallel replicas with bit-identical gradients stay bit-identical.  state[2] reports the norm also when max_norm <= 0.
+ * Non-finite gradients: with max_norm > 0 a NaN norm gives a NaN clip coefficient (min(1, NaN) = NaN, as clip_grad_norm_'s clamp), so
+ * EVERY element of p, m and v becomes NaN - a poisoned step is visible, never a silently unclipped one.  With max_norm <= 0 nothing
+ * couples the elements and only those whose own gradient is NaN are lost.  n == 0 returns at once and leaves state untouched. */
 #define CTTS_ADAM_PARTIALS 2048
 #define CTTS_ADAM_STATE_FLOATS (3 + CTTS_ADAM_PARTIALS)
 int ctts_adam_clip_step(float* p, const float* g, float* m, float* v, int64_t n, const float* lr, float beta1, float beta2, float eps,
@@ -517,7 +530,8 @@ int ctts_adam_clip_step(float* p, const float* g, float* m, float* v, int64_t n,
 /* Masked L1 of the two mel predictions in one pass (CompTransTTSLoss mel / postnet-mel terms, model/loss.py:130-138,
  * 303-304): rows with pad[row] != 0 count as zeros, w[row] = (sum_c |target[row,c]| != 0),
  *   sums = { sum w |p1 - t|, sum w |p2 - t|, sum w }  ->  loss_k = sums[k] / (C * sums[2]);   roww [rows] <- w (kept for backward);
- *   sums must be ZERO on entry (the kernel accumulates into it)
+ *   sums need NOT be initialised: its three floats are written, never accumulated into (rows == 0 writes three zeros).
+ *   ws: the stream's workspace (ordered multi-workgroup sum, same bits on every call) or NULL (one workgroup does all rows).
  * bwd: d1, d2 = g[k] * sign(p_k - t) * w / (C * sums[2]) with g the two upstream scalars (device). */
 int ctts_mel_l1_fwd(const float* p1, const float* p2, const float* tgt, const uint8_t* pad, float* sums, float* roww, int64_t rows,
                     int C, void* ws, void* stream);
