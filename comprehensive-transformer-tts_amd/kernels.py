@@ -1265,6 +1265,51 @@ def _vocoder_lens(lens, len_mul, B, what):
     return _p(lens), int(len_mul)
 
 
+def _f16c(t, name):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float16 and t.is_contiguous()):
+        raise _lib.CttsError(f"{name}: need a contiguous device float16 tensor")
+    return t
+
+
+def _vocoder_conv_desc(what, d, dtype, names, x, w, Cin, Cout, k, dil, transposed_u, slope, bias, R, out, alpha, beta, lens, len_mul):
+    """What vocoder_conv and vocoder_conv_h share (`what`: the wrapper's name, for the messages; x already checked for dtype and rank):
+    the shape, `out`, R, packed-weight and same-device checks, and the descriptor fields the two structs have in common.  `dtype` is
+    the wrapper's type of w, R and out (float32 / float16), `names` its message names for them.  -> out, allocated when not given."""
+    act = _f32c if dtype == torch.float32 else _f16c
+    B, T, cin = x.shape
+    if cin != Cin:
+        raise _lib.CttsError(f"{what}: x has {cin} channels, the layer {Cin}")
+    Tout = T * transposed_u if transposed_u else T
+    if out is None:
+        if beta != 0.0:
+            raise _lib.CttsError(f"{what}: beta != 0 needs `out`")
+        out = torch.empty(B, Tout, Cout, dtype=dtype, device=x.device)
+    elif tuple(out.shape) != (B, Tout, Cout):
+        raise _lib.CttsError(f"{what}: out has shape {tuple(out.shape)}, expected {(B, Tout, Cout)}")
+    if R is not None and tuple(R.shape) != (B, Tout, Cout):
+        raise _lib.CttsError(f"{what}: R has shape {tuple(R.shape)}, expected {(B, Tout, Cout)}")
+    N, taps = (transposed_u * Cout, k // transposed_u) if transposed_u else (Cout, k)
+    wshape = (-(-N // 128) * 128, taps * (-(-Cin // 32) * 32))
+    if tuple(act(w, names[0]).shape) != wshape:
+        raise _lib.CttsError(f"{what}: packed weight {tuple(w.shape)} does not match the layer (expected {wshape})")
+    for t, name in ((w, "weight"), (bias, "bias"), (R, "R"), (out, "out")):
+        if t is not None and t.device != x.device:
+            raise _lib.CttsError(f"{what}: {name} is on {t.device}, x on {x.device}")
+    d.x = _p(x)
+    d.sxb, d.sxt, d.sxc = (int(s) for s in x.stride())
+    d.B, d.T, d.Cin, d.Cout, d.k, d.dil = B, T, int(Cin), int(Cout), int(k), int(dil)
+    d.transposed_u = int(transposed_u)
+    d.act_in = 0 if slope is None else 1
+    d.slope = 0.0 if slope is None else float(slope)
+    d.w = _p(w)
+    d.bias = _p(None if bias is None else _f32c(bias, "bias"))
+    d.R = _p(None if R is None else act(R, names[1]))
+    d.out = _p(act(out, names[2]))
+    d.alpha, d.beta = float(alpha), float(beta)
+    d.lens, d.len_mul = _vocoder_lens(lens, len_mul, B, what)
+    return out
+
+
 def vocoder_conv(x, w, w_planes, Cin, Cout, k, dil=1, transposed_u=0, slope=None, bias=None, R=None, out=None, alpha=1.0, beta=0.0,
                  bf16_split=None, lens=None, len_mul=1):
     """One generator layer (include/ctts.h ctts_vocoder_conv).  x: [B, T, Cin] with any strides (fp32); w / w_planes from
@@ -1273,38 +1318,16 @@ def vocoder_conv(x, w, w_planes, Cin, Cout, k, dil=1, transposed_u=0, slope=None
     min(lens[b] len_mul, T) rows, computed as a B = 1 call on them would; output rows beyond its end are left unwritten."""
     if x.dtype != torch.float32 or x.dim() != 3:
         raise _lib.CttsError(f"vocoder_conv: x must be a 3-D float32 tensor [B, T, Cin], got {x.dtype} {tuple(x.shape)}")
-    B, T, cin = x.shape
-    if cin != Cin:
-        raise _lib.CttsError(f"vocoder_conv: x has {cin} channels, the layer {Cin}")
-    Tout = T * transposed_u if transposed_u else T
     split = BF16_SPLIT if bf16_split is None else int(bf16_split)
-    if out is None:
-        if beta != 0.0:
-            raise _lib.CttsError("vocoder_conv: beta != 0 needs `out`")
-        out = torch.empty(B, Tout, Cout, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, Tout, Cout):
-        raise _lib.CttsError(f"vocoder_conv: out has shape {tuple(out.shape)}, expected {(B, Tout, Cout)}")
     if split and w_planes is None:
         raise _lib.CttsError("vocoder_conv: the split arithmetic needs w_planes")
-    N, taps = (transposed_u * Cout, k // transposed_u) if transposed_u else (Cout, k)
-    wshape = (-(-N // 128) * 128, taps * (-(-Cin // 32) * 32))
-    if tuple(w.shape) != wshape or (split and w_planes.numel() != 3 * w.numel()):
-        raise _lib.CttsError(f"vocoder_conv: packed weight {tuple(w.shape)} does not match the layer (expected {wshape})")
     d = _lib.VconvDesc()
-    d.x = _p(x)
-    d.sxb, d.sxt, d.sxc = (int(s) for s in x.stride())
-    d.B, d.T, d.Cin, d.Cout, d.k, d.dil = B, T, int(Cin), int(Cout), int(k), int(dil)
-    d.transposed_u = int(transposed_u)
-    d.act_in = 0 if slope is None else 1
-    d.slope = 0.0 if slope is None else float(slope)
-    d.w = _p(_f32c(w, "vocoder weight"))
-    d.w_planes = None if (w_planes is None or not split) else _p(w_planes)
-    d.bias = _p(None if bias is None else _f32c(bias, "bias"))
-    d.R = _p(None if R is None else _f32c(R, "R"))
-    d.out = _p(_f32c(out, "out"))
-    d.alpha, d.beta = float(alpha), float(beta)
+    out = _vocoder_conv_desc("vocoder_conv", d, torch.float32, ("vocoder weight", "R", "out"), x, w, Cin, Cout, k, dil, transposed_u, slope,
+                             bias, R, out, alpha, beta, lens, len_mul)
+    if split and w_planes.numel() != 3 * w.numel():          # w has the layer's shape by now: the planes are not its split
+        raise _lib.CttsError(f"vocoder_conv: packed weight {tuple(w.shape)} does not match the layer (expected {tuple(w.shape)})")
+    d.w_planes = _p(w_planes) if split else None
     d.bf16_split = split
-    d.lens, d.len_mul = _vocoder_lens(lens, len_mul, B, "vocoder_conv")
     _lib.check(_lib.load().ctts_vocoder_conv(C.byref(d), _stream()), "ctts_vocoder_conv")
     return out
 
@@ -1338,12 +1361,6 @@ def vocoder_pack_weight_h(weight, transposed_u=0):
     return packed.clamp_(-FP16_MAX, FP16_MAX).to(torch.float16).contiguous()
 
 
-def _f16c(t, name):
-    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float16 and t.is_contiguous()):
-        raise _lib.CttsError(f"{name}: need a contiguous device float16 tensor")
-    return t
-
-
 def vocoder_conv_h(x, w, Cin, Cout, k, dil=1, transposed_u=0, slope=None, bias=None, R=None, out=None, alpha=1.0, beta=0.0,
                    lens=None, len_mul=1):
     """One generator layer in the fp16 mode (include/ctts.h ctts_vocoder_conv_h).  x: [B, T, Cin] with any strides, float32 (the mel:
@@ -1354,39 +1371,10 @@ def vocoder_conv_h(x, w, Cin, Cout, k, dil=1, transposed_u=0, slope=None, bias=N
                              f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
     if not x.is_cuda:
         raise _lib.CttsError("vocoder_conv_h: x must be a device (HIP) tensor")
-    B, T, cin = x.shape
-    if cin != Cin:
-        raise _lib.CttsError(f"vocoder_conv_h: x has {cin} channels, the layer {Cin}")
-    Tout = T * transposed_u if transposed_u else T
-    if out is None:
-        if beta != 0.0:
-            raise _lib.CttsError("vocoder_conv_h: beta != 0 needs `out`")
-        out = torch.empty(B, Tout, Cout, dtype=torch.float16, device=x.device)
-    elif tuple(out.shape) != (B, Tout, Cout):
-        raise _lib.CttsError(f"vocoder_conv_h: out has shape {tuple(out.shape)}, expected {(B, Tout, Cout)}")
-    if R is not None and tuple(R.shape) != (B, Tout, Cout):
-        raise _lib.CttsError(f"vocoder_conv_h: R has shape {tuple(R.shape)}, expected {(B, Tout, Cout)}")
-    N, taps = (transposed_u * Cout, k // transposed_u) if transposed_u else (Cout, k)
-    wshape = (-(-N // 128) * 128, taps * (-(-Cin // 32) * 32))
-    if tuple(_f16c(w, "vocoder_conv_h weight").shape) != wshape:
-        raise _lib.CttsError(f"vocoder_conv_h: packed weight {tuple(w.shape)} does not match the layer (expected {wshape})")
-    for t, name in ((w, "weight"), (bias, "bias"), (R, "R"), (out, "out")):
-        if t is not None and t.device != x.device:
-            raise _lib.CttsError(f"vocoder_conv_h: {name} is on {t.device}, x on {x.device}")
     d = _lib.VconvHDesc()
-    d.x = _p(x)
+    out = _vocoder_conv_desc("vocoder_conv_h", d, torch.float16, ("vocoder_conv_h weight", "vocoder_conv_h R", "vocoder_conv_h out"), x, w, Cin,
+                             Cout, k, dil, transposed_u, slope, bias, R, out, alpha, beta, lens, len_mul)
     d.x_f32 = 1 if x.dtype == torch.float32 else 0
-    d.sxb, d.sxt, d.sxc = (int(s) for s in x.stride())
-    d.B, d.T, d.Cin, d.Cout, d.k, d.dil = B, T, int(Cin), int(Cout), int(k), int(dil)
-    d.transposed_u = int(transposed_u)
-    d.act_in = 0 if slope is None else 1
-    d.slope = 0.0 if slope is None else float(slope)
-    d.w = _p(w)
-    d.bias = _p(None if bias is None else _f32c(bias, "bias"))
-    d.R = _p(None if R is None else _f16c(R, "vocoder_conv_h R"))
-    d.out = _p(_f16c(out, "vocoder_conv_h out"))
-    d.alpha, d.beta = float(alpha), float(beta)
-    d.lens, d.len_mul = _vocoder_lens(lens, len_mul, B, "vocoder_conv_h")
     _lib.check(_lib.load().ctts_vocoder_conv_h(C.byref(d), _stream()), "ctts_vocoder_conv_h")
     return out
 

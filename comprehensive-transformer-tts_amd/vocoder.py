@@ -23,10 +23,12 @@ The module call `g(mel, lens=None, precision=None)`: "fp32" (the default) is the
 csrc/vocoder_h.hip (include/ctts.h, "fp16 mode": fp16 weights and activations, one v_mfma_f32_32x32x16_f16 term per product, fp32
 accumulation, epilogue and conv_post; the wav is fp32 in both modes).  `precision=None` means `self.default_precision`, which the
 constructor takes from the environment variable CTTS_VOCODER_PRECISION (unset / "fp32" / "fp16") - the switch of the zero-edit drop-in
-route, whose `vocoder_infer` calls `vocoder(mels)`.  Each mode has its own packed-weight cache under the same invalidation rules, so the
-two can be mixed on one generator in any order.  `forward(mel, lens)` itself keeps the two-argument signature its callers and tests
+route, whose `vocoder_infer` calls `vocoder(mels)`.  Both precisions run the one layer schedule of `_forward`; a precision supplies its
+packer and kernels (`_Mode`) and has its own packed-weight cache slot under the same invalidation rules, so the two can be mixed on one
+generator in any order.  `forward(mel, lens)` itself keeps the two-argument signature its callers and tests
 know and runs the precision of the call in progress (`precision` of `g(...)`, else default_precision); `infer_wavs` keeps its
 signature too and follows the generator's default_precision.  `Generator.half()` is not the switch: it converts the parameters as on any nn.Module."""
+import collections
 import os
 
 import numpy as np
@@ -48,6 +50,20 @@ def _check_precision(p, what):
     if p not in PRECISIONS:
         raise ValueError(f"{what}: precision must be one of {PRECISIONS}, got {p!r}")
     return p
+
+
+# What a precision contributes to the forward: `key` tags its cache slot's key, pack(folded weight, transposed_u) -> the packed-weight
+# tuple, conv(x, packed + (bias,), Cin, Cout, k, dil, **epilogue) and post are its kernels.  The layer schedule is Generator._forward's.
+_Mode = collections.namedtuple("_Mode", "key pack conv post")
+
+
+def _mode(precision):
+    if precision == "fp16":           # weights folded in fp32, rounded once to fp16; biases and conv_post's weight stay fp32
+        return _Mode("fp16", lambda w, u: (K.vocoder_pack_weight_h(w, transposed_u=u),),
+                     lambda x, wb, *a, **kw: K.vocoder_conv_h(x, wb[0], *a, bias=wb[1], **kw), K.vocoder_post_h)
+    split = K.BF16_SPLIT
+    return _Mode(split, lambda w, u: K.vocoder_pack_weight(w, transposed_u=u, planes=split),
+                 lambda x, wpb, *a, **kw: K.vocoder_conv(x, wpb[0], wpb[1], *a, bias=wpb[2], bf16_split=split, **kw), K.vocoder_post)
 
 
 class AttrDict(dict):
@@ -129,10 +145,7 @@ class Generator(nn.Module):
             for k, d in zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes):
                 self.resblocks.append(ResBlock(h, ch, k, d))
         self.conv_post = _weight_norm(Conv1d(ch, 1, 7, 1, padding=3))
-        self._cache_key = None
-        self._cache = None
-        self._cache_h_key = None                              # the fp16 mode's own pack: neither mode rebuilds or reads the other's
-        self._cache_h = None
+        self._packs = {}                                      # precision -> (key, pack): neither mode rebuilds or reads the other's
         self._call_precision = None                           # set by __call__(..., precision=) for the duration of that call
         self.default_precision = _check_precision(os.environ.get(PRECISION_ENV) or "fp32", PRECISION_ENV)
 
@@ -162,21 +175,12 @@ class Generator(nn.Module):
             post = (wpost, self.conv_post.bias.detach().float().contiguous())
         return (pre, ups, rbs, post)
 
-    def _packed(self, split):
-        key = self._key(split)
-        if key != self._cache_key:
-            self._cache = self._build_pack(lambda w, u: K.vocoder_pack_weight(w, transposed_u=u, planes=split))
-            self._cache_key = key
-        return self._cache
-
-    def _packed_h(self):
-        """the fp16 mode's weights: folded in fp32, rounded once to fp16 and packed (kernels.vocoder_pack_weight_h); biases and
-        conv_post's weight stay fp32.  Its own cache slot under the same key rule: neither mode rebuilds or reads the other's."""
-        key = self._key("fp16")
-        if key != self._cache_h_key:
-            self._cache_h = self._build_pack(lambda w, u: (K.vocoder_pack_weight_h(w, transposed_u=u),))
-            self._cache_h_key = key
-        return self._cache_h
+    def _packed(self, precision, mode):
+        """the mode's packed weights from its own cache slot, rebuilt when its key changed"""
+        key = self._key(mode.key)
+        if precision not in self._packs or self._packs[precision][0] != key:
+            self._packs[precision] = (key, self._build_pack(mode.pack))
+        return self._packs[precision][1]
 
     # ---- forward -----------------------------------------------------------------------------------------------------------------
     def __call__(self, x, lens=None, precision=None):
@@ -219,33 +223,30 @@ class Generator(nn.Module):
         return lens.contiguous()
 
     def _forward(self, x, stage_cb=None, lens=None, precision=None):
-        """forward; stage_cb(name) after conv_pre, each upsampling stage and conv_post (tools/bench_vocoder.py's per-stage events)"""
+        """forward in either precision - the only copy of the layer schedule; stage_cb(name) after conv_pre, each upsampling stage and
+        conv_post (tools/bench_vocoder.py's per-stage events)"""
         precision = _check_precision(self.default_precision if precision is None else precision, "hifigan Generator")
         if not x.is_cuda:
             raise _lib.CttsError("hifigan Generator: the mel must be a device (HIP) tensor - there is no CPU path")
         if x.dim() != 3 or x.shape[1] != 80:
             raise _lib.CttsError(f"hifigan Generator: expected mel [B, 80, T], got {tuple(x.shape)}")
-        if precision == "fp16":
-            return self._forward_h(x, stage_cb, lens)
-        split = K.BF16_SPLIT
+        mode = _mode(precision)
         with torch.no_grad():
             if lens is not None:
                 lens = self._device_lens(lens, x)
             s = 1                                              # rows per mel frame of the current signal (the kernels' len_mul)
-            pre, ups, rbs, post = self._packed(split)
-            xt = x.float().transpose(1, 2)                     # [B, T, 80] channel-last view (the model's own mel layout)
-            c0 = self.h.upsample_initial_channel
-            w, wp, b = pre
-            hcur = K.vocoder_conv(xt, w, wp, 80, c0, 7, 1, bias=b, bf16_split=split, lens=lens, len_mul=s)     # models.py:146
+            pre, ups, rbs, post = self._packed(precision, mode)
+            xt = x.float().transpose(1, 2)                     # fp32 [B, T, 80] channel-last view (the model's own mel layout); the
+            c0 = self.h.upsample_initial_channel               # fp16 mode rounds it when the first layer stages it
+            hcur = mode.conv(xt, pre, 80, c0, 7, 1, lens=lens, len_mul=s)                                      # models.py:146
             if stage_cb:
                 stage_cb("conv_pre")
             nk = self.num_kernels
             for i in range(self.num_upsamples):
                 u, kup = self.h.upsample_rates[i], self.h.upsample_kernel_sizes[i]
                 cin, cout = c0 // (2 ** i), c0 // (2 ** (i + 1))
-                w, wp, b = ups[i]
-                hcur = K.vocoder_conv(hcur, w, wp, cin, cout, kup, 1, transposed_u=u, slope=LRELU_SLOPE, bias=b,   # models.py:148-149
-                                      bf16_split=split, lens=lens, len_mul=s)
+                hcur = mode.conv(hcur, ups[i], cin, cout, kup, 1, transposed_u=u, slope=LRELU_SLOPE, lens=lens,    # models.py:148-149
+                                 len_mul=s)
                 s *= u
                 xs = torch.empty_like(hcur)
                 for j in range(nk):                                                                            # models.py:150-158
@@ -253,67 +254,19 @@ class Generator(nn.Module):
                     k = rb.kernel_size
                     cur = hcur
                     for l, d in enumerate(rb.dilation):                                                         # models.py:96-104
-                        (w1, wp1, b1), (w2, wp2, b2) = rbs[i * nk + j][l]
-                        t = K.vocoder_conv(cur, w1, wp1, cout, cout, k, d, slope=LRELU_SLOPE, bias=b1, bf16_split=split,
-                                           lens=lens, len_mul=s)
+                        c1, c2 = rbs[i * nk + j][l]
+                        t = mode.conv(cur, c1, cout, cout, k, d, slope=LRELU_SLOPE, lens=lens, len_mul=s)
                         if l < len(rb.dilation) - 1:
-                            cur = K.vocoder_conv(t, w2, wp2, cout, cout, k, 1, slope=LRELU_SLOPE, bias=b2, R=cur, bf16_split=split,
-                                                 lens=lens, len_mul=s)
+                            cur = mode.conv(t, c2, cout, cout, k, 1, slope=LRELU_SLOPE, R=cur, lens=lens, len_mul=s)
                         else:             # xs = resblock_0(x); xs += resblock_j(x); x = xs / num_kernels - in the epilogue
                             last = j == nk - 1
-                            K.vocoder_conv(t, w2, wp2, cout, cout, k, 1, slope=LRELU_SLOPE, bias=b2, R=cur, out=xs,
-                                           alpha=1.0 / nk if last else 1.0, beta=0.0 if j == 0 else (1.0 / nk if last else 1.0),
-                                           bf16_split=split, lens=lens, len_mul=s)
+                            mode.conv(t, c2, cout, cout, k, 1, slope=LRELU_SLOPE, R=cur, out=xs, alpha=1.0 / nk if last else 1.0,
+                                      beta=0.0 if j == 0 else (1.0 / nk if last else 1.0), lens=lens, len_mul=s)
                 hcur = xs
                 if stage_cb:
                     stage_cb(f"stage{i}")
             wpost, bpost = post
-            wav = K.vocoder_post(hcur, wpost, bpost, POST_SLOPE, lens=lens, len_mul=s)                       # models.py:161-163
-            if stage_cb:
-                stage_cb("conv_post")
-            return wav
-
-
-    def _forward_h(self, x, stage_cb, lens):
-        """the fp16 mode (include/ctts.h): the launches of _forward on ctts_vocoder_conv_h / ctts_vocoder_post_h, fp16 activations"""
-        with torch.no_grad():
-            if lens is not None:
-                lens = self._device_lens(lens, x)
-            s = 1
-            pre, ups, rbs, post = self._packed_h()
-            xt = x.float().transpose(1, 2)                     # fp32 [B, T, 80] view: rounded to fp16 when the first layer stages it
-            c0 = self.h.upsample_initial_channel
-            w, b = pre
-            hcur = K.vocoder_conv_h(xt, w, 80, c0, 7, 1, bias=b, lens=lens, len_mul=s)
-            if stage_cb:
-                stage_cb("conv_pre")
-            nk = self.num_kernels
-            for i in range(self.num_upsamples):
-                u, kup = self.h.upsample_rates[i], self.h.upsample_kernel_sizes[i]
-                cin, cout = c0 // (2 ** i), c0 // (2 ** (i + 1))
-                w, b = ups[i]
-                hcur = K.vocoder_conv_h(hcur, w, cin, cout, kup, 1, transposed_u=u, slope=LRELU_SLOPE, bias=b, lens=lens, len_mul=s)
-                s *= u
-                xs = torch.empty_like(hcur)
-                for j in range(nk):
-                    rb = self.resblocks[i * nk + j]
-                    k = rb.kernel_size
-                    cur = hcur
-                    for l, d in enumerate(rb.dilation):
-                        (w1, b1), (w2, b2) = rbs[i * nk + j][l]
-                        t = K.vocoder_conv_h(cur, w1, cout, cout, k, d, slope=LRELU_SLOPE, bias=b1, lens=lens, len_mul=s)
-                        if l < len(rb.dilation) - 1:
-                            cur = K.vocoder_conv_h(t, w2, cout, cout, k, 1, slope=LRELU_SLOPE, bias=b2, R=cur, lens=lens, len_mul=s)
-                        else:
-                            last = j == nk - 1
-                            K.vocoder_conv_h(t, w2, cout, cout, k, 1, slope=LRELU_SLOPE, bias=b2, R=cur, out=xs,
-                                             alpha=1.0 / nk if last else 1.0, beta=0.0 if j == 0 else (1.0 / nk if last else 1.0),
-                                             lens=lens, len_mul=s)
-                hcur = xs
-                if stage_cb:
-                    stage_cb(f"stage{i}")
-            wpost, bpost = post
-            wav = K.vocoder_post_h(hcur, wpost, bpost, POST_SLOPE, lens=lens, len_mul=s)
+            wav = mode.post(hcur, wpost, bpost, POST_SLOPE, lens=lens, len_mul=s)                            # models.py:161-163
             if stage_cb:
                 stage_cb("conv_post")
             return wav

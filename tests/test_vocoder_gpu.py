@@ -109,6 +109,23 @@ def test_conv_pre_shape_and_strided_input():
         assert (a.double() - ref).abs().max().item() <= 1e-5
 
 
+def test_conv_rejects_a_misshaped_or_misplaced_R():
+    """R is read at out's offsets: one of another shape (here too short) would be read out of bounds, so it raises before any launch"""
+    from ctts_amd import _lib
+    g = torch.Generator(device="cpu").manual_seed(3)
+    B, T, C, k = 1, 4, 32, 3
+    x = torch.randn(B, T, C, generator=g).to(DEV)
+    w = (torch.randn(C, C, k, generator=g) / (C * k) ** 0.5).to(DEV)
+    for split in (1, 0):
+        for shape in ((B, T - 1, C), (B, T, C - 1), (T, C), (B, T, 2 * C)):
+            with pytest.raises(_lib.CttsError, match="R has shape"):
+                run_conv(x, w, None, 1, 0.1, split, R=torch.zeros(shape, device=DEV))
+        with pytest.raises(_lib.CttsError, match="R is on cpu"):
+            run_conv(x, w, None, 1, 0.1, split, R=torch.zeros(B, T, C))
+        Rr = torch.randn(B, T, C, generator=g).to(DEV)
+        assert (run_conv(x, w, None, 1, 0.1, split, R=Rr).double() - conv_ref64(x, w, None, 1, 0.1, Rr)).abs().max().item() <= 1e-5
+
+
 @pytest.mark.parametrize("cin,cout,k,u", [(512, 256, 16, 8), (256, 128, 16, 8), (128, 64, 4, 2), (64, 32, 4, 2)])
 def test_transposed_conv_vs_fp64(cin, cout, k, u):
     g = torch.Generator(device="cpu").manual_seed(cin + k)

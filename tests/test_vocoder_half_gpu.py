@@ -336,11 +336,52 @@ def test_fp16_reproducible_strided_and_mixed_with_fp32():
     assert torch.equal(g(mel, precision="fp16"), a)              # fp16, fp32, fp16: the first result again
     fresh, *_ = _g17_generator()
     assert torch.equal(fresh(mel), f)                            # the fp32 mode never saw the fp16 pack
-    key32, key16 = g._cache_key, g._cache_h_key
+    key32, key16 = g._packs["fp32"][0], g._packs["fp16"][0]
     g(mel, precision="fp16"), g(mel), g(mel, precision="fp16")
-    assert g._cache_key is key32 and g._cache_h_key is key16     # neither mode rebuilt the other's (or its own) cache
+    assert g._packs["fp32"][0] is key32 and g._packs["fp16"][0] is key16     # neither mode rebuilt the other's (or its own) cache
     g.default_precision = "fp16"
     assert torch.equal(g(mel), a)
+
+
+def test_both_precisions_launch_the_same_layer_schedule(monkeypatch):
+    """every launch of g(mel) and of g(mel, precision="fp16"), dense and ragged, recorded at the kernel wrappers: the two precisions run
+    the same layers with the same epilogue terms in the same order, 1 + nu + 6 nu nk + 1 of them"""
+    import inspect
+    g, z, h, _ = _g17_generator()
+    z20 = np.load(os.path.join(GOLD, "g20_hifigan_ragged.npz"))
+    lens = [int(v) for v in z20["mel_lens"]]
+    assert lens == [32, 13, 1, 27]
+    log = []
+
+    def record(name):
+        fn = getattr(K, name)
+        sig = inspect.signature(fn)
+
+        def wrapper(*args, **kw):
+            a = sig.bind(*args, **kw)
+            a.apply_defaults()
+            a = a.arguments
+            if "Cin" in a:
+                log.append((a["Cin"], a["Cout"], a["k"], a["dil"], a["transposed_u"], a["slope"], a["R"] is not None, a["out"] is not None,
+                            a["alpha"], a["beta"], a["len_mul"], a["lens"] is not None))
+            else:                                                # conv_post: x [B, T, C], w [k, C]
+                log.append((a["x"].shape[2], 1, a["w"].shape[0], 1, 0, a["slope"], False, a["out"] is not None, 1.0, 0.0, a["len_mul"],
+                            a["lens"] is not None))
+            return fn(*args, **kw)
+        monkeypatch.setattr(K, name, wrapper)
+
+    for name in ("vocoder_conv", "vocoder_post", "vocoder_conv_h", "vocoder_post_h"):
+        record(name)
+    nu, nk = g.num_upsamples, g.num_kernels
+    for mel, ln in ((torch.from_numpy(z["mel"]).to(DEV), None), (torch.from_numpy(z20["mel"]).to(DEV), lens)):
+        seqs = {}
+        for precision in ("fp32", "fp16"):
+            del log[:]
+            g(mel, lens=ln, precision=precision)
+            seqs[precision] = list(log)
+        assert seqs["fp32"] == seqs["fp16"]
+        assert len(seqs["fp32"]) == 1 + nu + 6 * nu * nk + 1
+        assert all(e[-1] == (ln is not None) for e in seqs["fp32"])
 
 
 def test_fp16_pack_follows_the_parameters():
