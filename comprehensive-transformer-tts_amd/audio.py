@@ -17,7 +17,8 @@ where it is available.
 
 Griffin-Lim (reference audio/stft.py:22-134 `STFT`, audio/audio_processing.py `griffin_lim` / `window_sumsquare` /
 `dynamic_range_*`, audio/tools.py:18-34 `inv_mel_spec`): `STFT.transform` / `inverse` and every Griffin-Lim iteration run on
-csrc/griffinlim.hip (a 1024-point real FFT per frame; one launch per iteration).  Supported: filter_length 1024, hop 256,
+csrc/griffinlim.hip (a 1024-point real FFT per frame; one launch per iteration, plain or with momentum = fast Griffin-Lim; the
+initial phase from numpy like the reference, as a tensor, or drawn on the device from a seed).  Supported: filter_length 1024, hop 256,
 win_length 1024, hann - an `STFT` of other sizes can be built (so can `TacotronSTFT`), its methods raise.
 """
 import math
@@ -196,28 +197,69 @@ class STFT(nn.Module):
         return self.inverse(self.magnitude, self.phase)
 
 
-def griffin_lim(magnitudes, stft_fn, n_iters=30, angles=None, lens=None):
+def _seed_arg(seed):
+    """seed of the device phase: None, a Python int (64 bits, taken modulo 2^64) or a one-element int64 tensor"""
+    if seed is None:
+        return None
+    if torch.is_tensor(seed):
+        if seed.dtype != torch.int64 or seed.numel() != 1:
+            raise ValueError(f"griffin_lim: a tensor seed must hold one int64, got {seed.dtype} x {seed.numel()}")
+        return seed
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError(f"griffin_lim: seed must be an int or a one-element int64 tensor, got {type(seed).__name__}")
+    v = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def griffin_lim(magnitudes, stft_fn, n_iters=30, angles=None, lens=None, momentum=0.0, seed=None):
     """audio_processing.py:66-82 on the kernels: magnitudes [B,513,F] (device) -> signal [B, 256 (F - 1)].
     angles=None draws the initial phase from numpy's GLOBAL generator exactly like the reference (np.random.seed(s) reproduces a
     reference run); an explicit device tensor [B,513,F] skips the host draw (and is capturable).  lens: frames per utterance of a ragged
     batch.  Launches: one inverse (frames), one per iteration (csrc/griffinlim.hip gl_iter_kernel, ping-pong frame buffers), one
-    overlap-add; no host synchronisation."""
+    overlap-add; no host synchronisation.
+    momentum in [0, 1): fast Griffin-Lim (Perraudin et al. 2013; librosa and torchaudio default to 0.99) - the rebuilt spectrum X of an
+    iteration is replaced by X - momentum / (1 + momentum) X_prev before its phase is taken; one state buffer per call holds X_prev.
+    0.0 is the reference's plain iteration, on the code path it always took.
+    seed (a Python int, or a one-element int64 device tensor - capturable, and a replay reads the tensor's value of that moment): the
+    initial phase is drawn on the device, theta(b, k, f) = 2 pi u(seed, b, k, f): no host draw, no [B,513,F] angle tensor, and an
+    utterance's start does not depend on the batch around it.  Not numpy's stream: np.random.seed does not reproduce it."""
     from . import kernels as K
     if not isinstance(stft_fn, STFT):
         raise TypeError("griffin_lim (ctts_amd): stft_fn must be a ctts_amd.audio.STFT (e.g. TacotronSTFT.stft_fn)")
+    momentum = float(momentum)
+    if not 0.0 <= momentum < 1.0:                          # NaN fails both comparisons
+        raise ValueError(f"griffin_lim: momentum must lie in [0, 1), got {momentum}")
+    seed = _seed_arg(seed)
+    if seed is not None and angles is not None:
+        raise ValueError("griffin_lim: pass either angles (an explicit initial phase) or seed (the device phase), not both")
     ws = stft_fn._workspace(magnitudes, "magnitudes")
     frames = stft_fn._frames(magnitudes, lens, 4)
-    if angles is None:
-        angles = np.angle(np.exp(2j * np.pi * np.random.rand(*magnitudes.size())))
-        angles = torch.from_numpy(angles.astype(np.float32)).to(magnitudes.device)
+    mag = magnitudes.float().contiguous()
+    if seed is not None:
+        if not torch.is_tensor(seed):
+            seed = torch.tensor([seed], dtype=torch.int64).to(mag.device)
+        elif seed.device != mag.device:
+            seed = seed.to(mag.device)
+        Y, magT = K.istft_frames_seeded(mag, ws, seed.view(1), frames, want_magT=n_iters > 0)
     else:
-        stft_fn._workspace(angles, "angles")
-    Y, magT = K.istft_frames(magnitudes.float().contiguous(), angles.float().contiguous(), ws, frames, want_magT=n_iters > 0)
+        if angles is None:
+            angles = np.angle(np.exp(2j * np.pi * np.random.rand(*magnitudes.size())))
+            angles = torch.from_numpy(angles.astype(np.float32)).to(magnitudes.device)
+        else:
+            stft_fn._workspace(angles, "angles")
+        Y, magT = K.istft_frames(mag, angles.float().contiguous(), ws, frames, want_magT=n_iters > 0)
     if n_iters > 0:
         Y2 = torch.empty_like(Y)
-        for _ in range(n_iters):
-            K.griffinlim_iter(Y, magT, ws, Y2, frames)
-            Y, Y2 = Y2, Y
+        if momentum == 0.0:
+            for _ in range(n_iters):
+                K.griffinlim_iter(Y, magT, ws, Y2, frames)
+                Y, Y2 = Y2, Y
+        else:
+            state = K.griffinlim_state(Y.shape[0], Y.shape[1], Y.device)
+            coef = momentum / (1.0 + momentum)
+            for i in range(n_iters):
+                K.griffinlim_iter_momentum(Y, magT, state, ws, Y2, coef, i == 0, frames)
+                Y, Y2 = Y2, Y
     return K.istft_ola(Y, ws, frames)
 
 
@@ -359,10 +401,10 @@ def get_mel_from_wav(audio, _stft):
     return _stft.mel_spectrograms_ragged([audio])[0]
 
 
-def inv_mel_spec(mel, out_filename, _stft, griffin_iters=60):
+def inv_mel_spec(mel, out_filename, _stft, griffin_iters=60, momentum=0.0, seed=None):
     """audio/tools.py:18-34: log-mel [n_mel, F] (device tensor) -> float32 wav at _stft.sampling_rate through Griffin-Lim, bug for bug:
     exp(mel) times the filterbank itself (not a pseudo-inverse), * 1000, the last frame dropped.  One deliberate deviation: the reference
-    reads `_stft._stft_fn`, which does not exist (AttributeError); this version uses `_stft.stft_fn`."""
+    reads `_stft._stft_fn`, which does not exist (AttributeError); this version uses `_stft.stft_fn`.  momentum / seed: griffin_lim's."""
     from scipy.io.wavfile import write
     if not torch.is_tensor(mel) or not mel.is_cuda:
         raise RuntimeError("inv_mel_spec (ctts_amd) computes on the MI355X: pass the mel as a device tensor")
@@ -370,5 +412,5 @@ def inv_mel_spec(mel, out_filename, _stft, griffin_iters=60):
         _stft.to(mel.device)
     # spectral_de_normalize (exp, C = 1), the filterbank applied transposed, the fixed gain; drop the last frame, then Griffin-Lim
     spec = (torch.exp(mel).t() @ _stft.mel_basis).t().unsqueeze(0) * 1000.0     # [1, 513, F]
-    wav = griffin_lim(spec[:, :, :-1], _stft.stft_fn, griffin_iters)[0]
+    wav = griffin_lim(spec[:, :, :-1], _stft.stft_fn, griffin_iters, momentum=momentum, seed=seed)[0]
     write(out_filename, _stft.sampling_rate, wav.cpu().numpy())

@@ -17,6 +17,14 @@
 // Y_in to Y_out: each wave gathers the signal under its frame (with the reflect padding of transform at both ends of the utterance, as
 // index arithmetic), runs the forward FFT, rescales every bin to the target magnitude (X |X|^-1 = cos / sin of atan2, (1, 0) at |X| = 0),
 // runs the inverse FFT and writes its windowed frame.  Ragged batches: per-utterance frame counts; every utterance reflects at its own end.
+//
+// Fast Griffin-Lim (Perraudin, Balazs, Sondergaard 2013; the momentum of librosa / torchaudio): the same launch with a per-frame STATE
+// slot that holds the previous iteration's rebuilt spectrum T.  With X the rebuilt spectrum of this iteration: A = X - coef T, T <- X,
+// and A (not X) is rescaled to the target magnitude; coef = momentum / (1 + momentum).  A slot is laid out by lane ownership (what
+// split_bins leaves in a lane's registers: float4 (X[k], X[512 - k]) at [m][lane], k = lane + 64 m, then bin 256), is read and rewritten
+// by the one wave that owns the frame, each lane its own bytes - in place, no third buffer, no hazard between waves.
+// The initial phase can be drawn on the device: theta(b, k, f) = 2 pi u, u in [0, 1) from ctts_mix32 chained over (seed, b, f, k) - a
+// pure function of those four, so an utterance's start does not depend on the batch around it, and no [B, 513, F] angle tensor exists.
 #include <float.h>
 #include "ctts_common.h"
 
@@ -29,6 +37,7 @@ constexpr int WS_W512 = 0, WS_W1024 = 1024, WS_WIN = 1540, WS_W2 = WS_WIN + NFFT
 // LDS: W512 | W1024 | the 7 x 8 twiddles of FFT pass 1 | window^2 | 4 waves x scratch
 constexpr int LDS_TW1 = 1540, LDS_W2 = 1540 + 112, LDS_SCR = LDS_W2 + NFFT, LDS_FLOATS = LDS_SCR + 4 * 2 * SCR;
 constexpr int MAX_GRID = 1024;             // workgroups of a frame launch: 4 per CU of the 256, each wave walks its frames
+constexpr int STATE_SLOT = 4 * 256 + 4;    // floats of a frame's momentum state: float4 (X[k], X[512 - k]) [4][64] | X[256] | 2 floats of padding
 
 struct float2_ { float x, y; };
 __device__ __forceinline__ float2_ cmul(float2_ a, float2_ b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
@@ -215,16 +224,30 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, 
   }
 }
 
+// counter-based initial phase: u(seed, b, k, f) in [0, 1) with 24 bits, the dropout kernels' generator chained over b, f and k
+constexpr uint32_t GL_PHASE_SITE = 0x474C5048U;          // call-site offset of ctts_drop_key
+__device__ __forceinline__ uint32_t phase_frame_key(uint32_t key, int b, int f) {
+  return ctts_mix32(ctts_mix32(key + (uint32_t)b * CTTS_DROP_G) + (uint32_t)f * CTTS_DROP_G);
+}
+__device__ __forceinline__ float phase_u(uint32_t fkey, int k) {
+  return (float)(ctts_mix32(fkey + (uint32_t)k * CTTS_DROP_G) >> 8) * (1.0f / 16777216.0f);
+}
+
 // ------------------------------------------------------------------------------------------------ inverse, part 1: (mag, phase) -> Y
+// SEEDED: the phase is not read but drawn, theta = 2 pi phase_u; (cos, sin)(theta) = sincospi(2 u), exact in the argument
+template <bool SEEDED>
 __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restrict__ mag, const float* __restrict__ phase, long sb, long sk, long sf,
                                                            const int32_t* __restrict__ frames, const float* __restrict__ ws,
-                                                           float* __restrict__ Y, float* __restrict__ magT, int B, int F) {
+                                                           float* __restrict__ Y, float* __restrict__ magT, int B, int F,
+                                                           const int64_t* __restrict__ seed) {
   __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   load_tables(lds, ws, tid);
   float win[16];
   load_window(ws, lane, win);
   float* S = lds + LDS_SCR + wave * 2 * SCR;
+  uint32_t key = 0;
+  if (SEEDED) key = ctts_drop_key(reinterpret_cast<const uint64_t*>(seed), GL_PHASE_SITE);
   __syncthreads();
   const long total = (long)B * F;
   for (long gf = (long)blockIdx.x * 4 + wave; gf < total; gf += (long)gridDim.x * 4) {
@@ -232,7 +255,12 @@ __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restri
     const int Fb = frames ? min(max(frames[b], 2), F) : F;
     if (f >= Fb) continue;
     const float* mb = mag + b * sb + f * sf;
-    const float* pb = phase + b * sb + f * sf;
+    const float* pb = SEEDED ? nullptr : phase + b * sb + f * sf;
+    const uint32_t fkey = SEEDED ? phase_frame_key(key, b, f) : 0u;
+    auto unit = [&](int k, float* s, float* co) {
+      if (SEEDED) sincospif(2.0f * phase_u(fkey, k), s, co);
+      else sincosf(pb[k * sk], s, co);
+    };
     float* mt = magT ? magT + gf * NBINS : nullptr;
     float2_ xk[4], xm[4], x256;
 #pragma unroll
@@ -240,14 +268,14 @@ __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restri
       const int k = lane + 64 * m, km = 512 - k;
       const float a = mb[k * sk], c = mb[km * sk];
       float s, co;
-      sincosf(pb[k * sk], &s, &co); xk[m] = {a * co, a * s};
-      sincosf(pb[km * sk], &s, &co); xm[m] = {c * co, c * s};
+      unit(k, &s, &co); xk[m] = {a * co, a * s};
+      unit(km, &s, &co); xm[m] = {c * co, c * s};
       if (mt) { mt[k] = a; mt[km] = c; }
     }
     {
       const float a = mb[256 * sk];
       float s, co;
-      sincosf(pb[256 * sk], &s, &co);
+      unit(256, &s, &co);
       x256 = {a * co, a * s};
       if (mt && lane == 0) mt[256] = a;
     }
@@ -257,8 +285,11 @@ __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ one Griffin-Lim iteration: Y_in -> Y_out
+// MOM: the fast Griffin-Lim update through the frame's state slot (see the head of the file); first: the state counts as zero, is not read
+template <bool MOM>
 __global__ __launch_bounds__(256) void gl_iter_kernel(const float* __restrict__ Yin, const float* __restrict__ magT, const int32_t* __restrict__ frames,
-                                                      const float* __restrict__ ws, float* __restrict__ Yout, int B, int F) {
+                                                      const float* __restrict__ ws, float* __restrict__ Yout, int B, int F,
+                                                      float* __restrict__ state, float coef, int first) {
   __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   load_tables(lds, ws, tid);
@@ -274,6 +305,15 @@ __global__ __launch_bounds__(256) void gl_iter_kernel(const float* __restrict__ 
     if (f >= Fb) continue;
     const int L = HOP * (Fb - 1);
     const float* Yb = Yin + (long)b * F * NFFT;
+    // the previous rebuilt spectrum: loaded ahead of the gather and the FFT, which hide its latency
+    float4 tp[4] = {};
+    float2 tp256 = {};
+    float* st = MOM ? state + gf * STATE_SLOT : nullptr;
+    if (MOM && !first) {
+#pragma unroll
+      for (int m = 0; m < 4; ++m) tp[m] = reinterpret_cast<const float4*>(st)[m * 64 + lane];
+      if (lane == 0) tp256 = *reinterpret_cast<const float2*>(st + 1024);
+    }
     // transform of the previous signal: frame f covers output samples u = 256 f - 512 + n, reflected at 0 and L - 1
     float2_ v[8];
     const int base = f * HOP - NFFT / 2;
@@ -293,6 +333,16 @@ __global__ __launch_bounds__(256) void gl_iter_kernel(const float* __restrict__ 
     fft512(v, S, lds + WS_W512, lds + LDS_TW1, lane);
     float2_ xk[4], xm[4], x256;
     split_bins(S, lds + WS_W1024, lane, xk, xm, x256);
+    if (MOM) {                                          // T <- X, then X <- A = X - coef T_prev (bin 256 lives in lane 0 alone: merge_bins)
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        reinterpret_cast<float4*>(st)[m * 64 + lane] = make_float4(xk[m].x, xk[m].y, xm[m].x, xm[m].y);
+        xk[m] = {xk[m].x - coef * tp[m].x, xk[m].y - coef * tp[m].y};
+        xm[m] = {xm[m].x - coef * tp[m].z, xm[m].y - coef * tp[m].w};
+      }
+      if (lane == 0) *reinterpret_cast<float2*>(st + 1024) = make_float2(x256.x, x256.y);
+      x256 = {x256.x - coef * tp256.x, x256.y - coef * tp256.y};
+    }
     // keep the phase, take the target magnitude: mag * (cos, sin)(atan2(im, re)) = mag * X / |X|, (mag, 0) where |X| = 0
     const float* mt = magT + gf * NBINS;
     auto rescale = [](float2_ z, float a) -> float2_ {
@@ -372,9 +422,20 @@ extern "C" int ctts_istft_frames(const float* mag, const float* phase, int64_t s
   CTTS_REQUIRE(mag && phase && workspace && Y && B > 0, "ctts_istft_frames: bad arguments");
   CTTS_REQUIRE(n_fft == NFFT && hop == HOP, "ctts_istft_frames: built for n_fft = 1024, hop = 256; got %d / %d", n_fft, hop);
   CTTS_REQUIRE(F >= 2, "ctts_istft_frames: needs at least 2 frames (got %d)", F);
-  hipLaunchKernelGGL(istft_frames_kernel, dim3(frame_grid((long)B * F)), dim3(256), 0, (hipStream_t)stream, mag, phase, (long)sb, (long)sk,
-                     (long)sf, frames, workspace, Y, magT, B, F);
+  hipLaunchKernelGGL(istft_frames_kernel<false>, dim3(frame_grid((long)B * F)), dim3(256), 0, (hipStream_t)stream, mag, phase, (long)sb,
+                     (long)sk, (long)sf, frames, workspace, Y, magT, B, F, (const int64_t*)nullptr);
   CTTS_CHECK_LAUNCH("ctts_istft_frames");
+  return 0;
+}
+
+extern "C" int ctts_istft_frames_seeded(const float* mag, int64_t sb, int64_t sk, int64_t sf, const int32_t* frames, const float* workspace,
+                                        const int64_t* seed, float* Y, float* magT, int B, int F, int n_fft, int hop, void* stream) {
+  CTTS_REQUIRE(mag && workspace && seed && Y && B > 0, "ctts_istft_frames_seeded: bad arguments");
+  CTTS_REQUIRE(n_fft == NFFT && hop == HOP, "ctts_istft_frames_seeded: built for n_fft = 1024, hop = 256; got %d / %d", n_fft, hop);
+  CTTS_REQUIRE(F >= 2, "ctts_istft_frames_seeded: needs at least 2 frames (got %d)", F);
+  hipLaunchKernelGGL(istft_frames_kernel<true>, dim3(frame_grid((long)B * F)), dim3(256), 0, (hipStream_t)stream, mag, (const float*)nullptr,
+                     (long)sb, (long)sk, (long)sf, frames, workspace, Y, magT, B, F, seed);
+  CTTS_CHECK_LAUNCH("ctts_istft_frames_seeded");
   return 0;
 }
 
@@ -383,8 +444,25 @@ extern "C" int ctts_griffinlim_iter(const float* Y_in, const float* magT, const 
   CTTS_REQUIRE(Y_in && magT && workspace && Y_out && Y_in != Y_out && B > 0, "ctts_griffinlim_iter: bad arguments");
   CTTS_REQUIRE(n_fft == NFFT && hop == HOP, "ctts_griffinlim_iter: built for n_fft = 1024, hop = 256; got %d / %d", n_fft, hop);
   CTTS_REQUIRE(F >= 4, "ctts_griffinlim_iter: needs at least 4 frames (got %d)", F);
-  hipLaunchKernelGGL(gl_iter_kernel, dim3(frame_grid((long)B * F)), dim3(256), 0, (hipStream_t)stream, Y_in, magT, frames, workspace, Y_out, B, F);
+  hipLaunchKernelGGL(gl_iter_kernel<false>, dim3(frame_grid((long)B * F)), dim3(256), 0, (hipStream_t)stream, Y_in, magT, frames, workspace,
+                     Y_out, B, F, (float*)nullptr, 0.f, 0);
   CTTS_CHECK_LAUNCH("ctts_griffinlim_iter");
+  return 0;
+}
+
+extern "C" size_t ctts_griffinlim_state_floats(int B, int F) {
+  return B > 0 && F > 0 ? (size_t)B * (size_t)F * STATE_SLOT : 0;
+}
+
+extern "C" int ctts_griffinlim_iter_momentum(const float* Y_in, const float* magT, float* state, const int32_t* frames, const float* workspace,
+                                             float* Y_out, float coef, int first, int B, int F, int n_fft, int hop, void* stream) {
+  CTTS_REQUIRE(Y_in && magT && state && workspace && Y_out && Y_in != Y_out && B > 0, "ctts_griffinlim_iter_momentum: bad arguments");
+  CTTS_REQUIRE(n_fft == NFFT && hop == HOP, "ctts_griffinlim_iter_momentum: built for n_fft = 1024, hop = 256; got %d / %d", n_fft, hop);
+  CTTS_REQUIRE(F >= 4, "ctts_griffinlim_iter_momentum: needs at least 4 frames (got %d)", F);
+  CTTS_REQUIRE(coef >= 0.f && coef < 1.f, "ctts_griffinlim_iter_momentum: coef = momentum / (1 + momentum) must lie in [0, 1), got %g", (double)coef);
+  hipLaunchKernelGGL(gl_iter_kernel<true>, dim3(frame_grid((long)B * F)), dim3(256), 0, (hipStream_t)stream, Y_in, magT, frames, workspace,
+                     Y_out, B, F, state, coef, first);
+  CTTS_CHECK_LAUNCH("ctts_griffinlim_iter_momentum");
   return 0;
 }
 

@@ -1533,6 +1533,41 @@ def griffinlim_iter(Y_in, magT, ws, Y_out, frames=None):
     return Y_out
 
 
+def griffinlim_state(B, F, device):
+    """the state buffer of griffinlim_iter_momentum for frame buffers [B,F,1024]: one slot per frame (the previous rebuilt spectrum),
+    uninitialised - the first iteration (first=True) only writes it"""
+    return torch.empty(_lib.load().ctts_griffinlim_state_floats(int(B), int(F)), dtype=torch.float32, device=device)
+
+
+def griffinlim_iter_momentum(Y_in, magT, state, ws, Y_out, coef, first, frames=None):
+    """one fast Griffin-Lim iteration (Y_in -> Y_out, [B,F,1024]): A = X - coef T_prev, T_prev <- X in `state` (griffinlim_state), A
+    rescaled to magT [B,F,513]; coef = momentum / (1 + momentum); first: the state counts as zero and is only written"""
+    B, F, _ = Y_in.shape
+    lib = _lib.load()
+    if not state.is_cuda or state.dtype != torch.float32 or not state.is_contiguous() or state.numel() < lib.ctts_griffinlim_state_floats(B, F):
+        raise _lib.CttsError(f"griffinlim_iter_momentum: state must be a contiguous float32 device tensor of griffinlim_state({B}, {F})")
+    _lib.check(lib.ctts_griffinlim_iter_momentum(_p(_f32c(Y_in, "Y_in")), _p(_f32c(magT, "magT")), _p(state), _p(_frames_arg(frames)), _p(ws),
+                                                 _p(_f32c(Y_out, "Y_out")), float(coef), int(bool(first)), B, F, GL_NFFT, GL_HOP, _stream()),
+               "ctts_griffinlim_iter_momentum")
+    return Y_out
+
+
+def istft_frames_seeded(mag, ws, seed, frames=None, want_magT=False):
+    """istft_frames with the initial phase drawn on the device: theta(b, k, f) = 2 pi u(seed, b, k, f).  mag [B,513,F] contiguous,
+    seed a one-element int64 device tensor (read by the kernel) -> (Y [B,F,1024], frame-major magnitude copy [B,F,513] or None)"""
+    B, nb, F = mag.shape
+    if nb != GL_NBINS:
+        raise _lib.CttsError(f"istft_frames_seeded: expected magnitude [B, 513, F], got {tuple(mag.shape)}")
+    if not torch.is_tensor(seed) or not seed.is_cuda or seed.dtype != torch.int64 or seed.numel() != 1:
+        raise _lib.CttsError("istft_frames_seeded: seed must be a one-element int64 device tensor")
+    Y = torch.empty(B, F, GL_NFFT, dtype=torch.float32, device=mag.device)
+    magT = torch.empty(B, F, GL_NBINS, dtype=torch.float32, device=mag.device) if want_magT else None
+    lib = _lib.load()
+    _lib.check(lib.ctts_istft_frames_seeded(_p(_f32c(mag, "magnitude")), GL_NBINS * F, F, 1, _p(_frames_arg(frames)), _p(ws), _p(seed),
+                                            _p(Y), _p(magT), B, F, GL_NFFT, GL_HOP, _stream()), "ctts_istft_frames_seeded")
+    return Y, magT
+
+
 def istft_ola(Y, ws, frames=None, out=None):
     """Y [B,F,1024] -> waveform [B, 256 (F - 1)] (overlap-add, window-sum division, * 4, crop)"""
     B, F, _ = Y.shape

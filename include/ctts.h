@@ -673,10 +673,19 @@ int ctts_fastformer_resdrop(const float* x, const float* t, float* y, float* y2,
  *              [B][F][513]) receives a frame-major copy of mag, the operand of griffinlim_iter.
  *   griffinlim_iter  Y_in -> Y_out (distinct buffers): overlap-add of Y_in, transform with reflect padding, magnitude replaced by magT
  *              (phase kept; (mag, 0) where |X| = 0), inverse - one Griffin-Lim iteration.
+ *   griffinlim_iter_momentum  the same launch as one iteration of fast Griffin-Lim (Perraudin et al. 2013, the momentum of librosa /
+ *              torchaudio): with X the rebuilt spectrum, A = X - coef T_prev, T_prev <- X, and A is rescaled to magT by the rule above
+ *              (m A / |A|, (m, 0) where |A| = 0; not librosa's + 1e-16).  coef = momentum / (1 + momentum), in [0, 1).  state
+ *              (griffinlim_state_floats(B, F) floats, one slot per frame, layout private to the library) holds T_prev; a slot is read
+ *              and rewritten in place by the one wave that owns the frame.  first != 0: the state counts as zero and is only written
+ *              (it need not be initialised, NaN included).  coef = 0 gives griffinlim_iter's bits.
+ *   istft_frames_seeded  istft_frames with the phase drawn on the device instead of read: theta(b, k, f) = 2 pi u, u in [0, 1) a
+ *              counter-based hash (the dropout kernels' ctts_mix32) of (*seed, b, k, f) alone - not of B, F or frames.  seed is a
+ *              DEVICE int64, read by the kernel: a captured graph replays with whatever it holds then.
  *   istft_ola  Y -> out [B, ld_out >= 256 (F - 1)]: overlap-add in ascending frame order, / window_sumsquare where > FLT_MIN, * 4, crop
  *              512 at both ends; samples past 256 (frames[b] - 1) are written as 0.
- * frames (device int32 [B] or NULL = F): frames per utterance of a ragged batch.  istft_frames / istft_ola need F >= 2 and clamp
- *   frames[b] to [2, F]; griffinlim_iter needs F >= 4 and clamps to [4, F] (its transform needs more than n_fft/2 samples). */
+ * frames (device int32 [B] or NULL = F): frames per utterance of a ragged batch.  istft_frames(_seeded) / istft_ola need F >= 2 and clamp
+ *   frames[b] to [2, F]; griffinlim_iter(_momentum) needs F >= 4 and clamps to [4, F] (its transform needs more than n_fft/2 samples). */
 size_t ctts_griffinlim_workspace_bytes(int n_fft, int hop);
 int ctts_griffinlim_prepare(const float* window, int n_fft, int hop, float* workspace, void* stream);
 int ctts_stft_transform(const float* x, const int32_t* lens, const float* workspace, float* mag, float* phase, int64_t sb, int64_t sk,
@@ -687,6 +696,11 @@ int ctts_griffinlim_iter(const float* Y_in, const float* magT, const int32_t* fr
                          int n_fft, int hop, void* stream);
 int ctts_istft_ola(const float* Y, const int32_t* frames, const float* workspace, float* out, int64_t ld_out, int B, int F, int n_fft,
                    int hop, void* stream);
+size_t ctts_griffinlim_state_floats(int B, int F);
+int ctts_griffinlim_iter_momentum(const float* Y_in, const float* magT, float* state, const int32_t* frames, const float* workspace,
+                                  float* Y_out, float coef, int first, int B, int F, int n_fft, int hop, void* stream);
+int ctts_istft_frames_seeded(const float* mag, int64_t sb, int64_t sk, int64_t sf, const int32_t* frames, const float* workspace,
+                             const int64_t* seed, float* Y, float* magT, int B, int F, int n_fft, int hop, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (SURVEY.md section 8(b) `ctts_allreduce_*`, 8(e); replaces what
