@@ -1578,3 +1578,82 @@ def istft_ola(Y, ws, frames=None, out=None):
     _lib.check(lib.ctts_istft_ola(_p(_f32c(Y, "Y")), _p(_frames_arg(frames)), _p(ws), _p(_f32c(out, "out")), out.shape[-1], B, F,
                                   GL_NFFT, GL_HOP, _stream()), "ctts_istft_ola")
     return out
+
+
+# ---- pitch targets: F0 tracker and the F0 -> continuous log-F0 -> CWT chain (csrc/pitchtrack.hip) -----------------------------
+F0T_MAX_FRAMES, F0T_NSCALE = 4096, 10
+
+
+def _al4(t, name):
+    if t.data_ptr() % 4:
+        raise _lib.CttsError(f"{name}: the data pointer must be 4-byte aligned")
+    return t
+
+
+def pitch_track_prepare(device):
+    """-> workspace tensor of `pitch_track` (FFT twiddles, hann window and the window's normalised autocorrelation)"""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.CttsError("pitch_track_prepare: needs a HIP device - no CPU fallback exists")
+    lib = _lib.load()
+    ws = torch.empty(lib.ctts_pitch_track_workspace_bytes() // 4, dtype=torch.float32, device=device)
+    _lib.check(lib.ctts_pitch_track_prepare(_p(ws), _stream()), "ctts_pitch_track_prepare")
+    return ws
+
+
+def pitch_track(wav, ws, lens=None, sr=22050, hop=256, f0_min=80.0, f0_max=750.0, voicing_threshold=0.6, silence_threshold=0.03):
+    """wav [B,N] float32, lens int32 [B] samples or None -> (f0 [B,F] Hz, 0 = unvoiced; strength [B,F]), F = 1 + N // hop"""
+    if not torch.is_tensor(wav) or wav.dim() != 2:
+        raise _lib.CttsError("pitch_track: expected wav [B, N]")
+    B, N = wav.shape
+    if B < 1 or N < 1:
+        raise _lib.CttsError(f"pitch_track: empty batch {tuple(wav.shape)}")
+    _p(wav)                                                # CPU tensor -> CttsError
+    _al4(_f32c(wav, "wav"), "wav")
+    if lens is not None and (_frames_arg(lens).numel() != B):
+        raise _lib.CttsError(f"pitch_track: {lens.numel()} lengths for a batch of {B}")
+    if int(hop) < 1:
+        raise _lib.CttsError(f"pitch_track: hop must be >= 1, got {hop}")
+    F = 1 + N // int(hop)
+    f0 = torch.empty(B, F, dtype=torch.float32, device=wav.device)
+    strength = torch.empty_like(f0)
+    peak = torch.empty(B * 32, dtype=torch.float32, device=wav.device)          # scratch: the utterance peaks, 32 slices each
+    _lib.check(_lib.load().ctts_pitch_track(_p(wav), _p(lens), _p(_f32c(ws, "workspace")), _p(peak), _p(f0), _p(strength), B, N, int(sr), int(hop),
+                                            float(f0_min), float(f0_max), float(voicing_threshold), float(silence_threshold), _stream()),
+               "ctts_pitch_track")
+    return f0, strength
+
+
+def _f0_frames_args(f0, frames, what):
+    if not torch.is_tensor(f0) or f0.dim() != 2:
+        raise _lib.CttsError(f"{what}: expected f0 [B, F]")
+    _p(f0)
+    _al4(_f32c(f0, "f0"), "f0")
+    B, F = f0.shape
+    if B < 1 or F < 1:
+        raise _lib.CttsError(f"{what}: empty batch {tuple(f0.shape)}")
+    if frames is None or not torch.is_tensor(frames) or _frames_arg(frames).numel() != B:
+        raise _lib.CttsError(f"{what}: frames must be an int32 device tensor with one entry per utterance")
+    return B, F
+
+
+def f0_targets(f0, frames):
+    """f0 [B,F] Hz (0 = unvoiced), frames int32 [B] -> (uv [B,F], cont_lf0 [B,F], mean_std [B,2], cwt_spec [B,F,10], valid int32 [B])"""
+    B, F = _f0_frames_args(f0, frames, "f0_targets")
+    dev = f0.device
+    uv = torch.empty(B, F, dtype=torch.float32, device=dev)
+    cont = torch.empty_like(uv)
+    mean_std = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    cwt = torch.empty(B, F, F0T_NSCALE, dtype=torch.float32, device=dev)
+    valid = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().ctts_f0_targets(_p(f0), _p(frames), _p(uv), _p(cont), _p(mean_std), _p(cwt), _p(valid), B, F, _stream()), "ctts_f0_targets")
+    return uv, cont, mean_std, cwt, valid
+
+
+def norm_interp_f0(f0, frames, eps=1e-9):
+    """f0 [B,F] Hz, frames int32 [B] -> (log2 f0 interpolated over the unvoiced frames [B,F], uv [B,F])"""
+    B, F = _f0_frames_args(f0, frames, "norm_interp_f0")
+    out = torch.empty(B, F, dtype=torch.float32, device=f0.device)
+    uv = torch.empty_like(out)
+    _lib.check(_lib.load().ctts_norm_interp_f0(_p(f0), _p(frames), _p(out), _p(uv), B, F, float(eps), _stream()), "ctts_norm_interp_f0")
+    return out, uv

@@ -724,6 +724,45 @@ int ctts_comm_create(void** comm_out, int32_t nranks, int32_t rank, const void* 
 int ctts_comm_destroy(void* comm);
 int ctts_allreduce_mean(float* buf, int64_t n, void* comm, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Pitch targets on the device (csrc/pitchtrack.hip): wav -> f0 -> the p_targets of the cwt pitch branch.
+ *
+ * ctts_pitch_track: a batched, length-aware F0 tracker (Boersma-style autocorrelation; a specified algorithm of this project, NOT a
+ * clone of parselmouth's to_pitch_ac, which the reference calls at utils/pitch_tools.py:106-108 - no path search across frames).
+ *   wav [B,N] fp32 in [-1,1]; lens [B] int32 samples per utterance (NULL = N); f0 [B,F] Hz (0 = unvoiced), strength [B,F],
+ *   F = 1 + N / hop: the mel kernel's framing, frame t centred at sample t hop, samples outside [0, len) read as 0, frames at or
+ *   beyond 1 + len / hop give 0.  Per frame: 1024 samples, minus their mean, times the periodic hann window; 2048-point zero-padded
+ *   power spectrum and back = autocorrelation r; rn(tau) = (r(tau) / r(0)) / (r_w(tau) / r_w(0)) with the window's own
+ *   autocorrelation r_w (workspace); candidates = local maxima (rn(tau) > rn(tau-1) and rn(tau) >= rn(tau+1)) over the integer lags
+ *   [floor(sr / f0_max), ceil(sr / f0_min)], lag and height refined by a parabola through the three points; the winner maximises
+ *   height - 0.01 log2(f0_min tau / sr) (ties: the smaller lag); voiced when its height >= voicing_threshold and the frame's peak |x|
+ *   >= silence_threshold * the utterance's peak |x| over [0, len).  r(0) <= 0 or non-finite (digital silence, NaN input) and frames
+ *   without a candidate give f0 = strength = 0; an unvoiced frame with a candidate keeps its strength.
+ *   DOMAIN: hop >= 1, 0 < f0_min < f0_max, floor(sr / f0_max) >= 2 and ceil(sr / f0_min) + 1 < 512 (the lags, with one neighbour
+ *   on each side, stay inside the first half of the 1024-sample frame, where r_w is far from 0); anything else is refused with an
+ *   error string before any launch.  peak [32 B]: scratch of the call (the utterance peaks in 32 slices each, a launch of their own).
+ *   workspace: ctts_pitch_track_workspace_bytes() bytes, filled once by ctts_pitch_track_prepare (twiddles and r_w in double precision).
+ *   No float atomics, no inter-workgroup waits: bit-reproducible, and an utterance's result does not depend on the batch around it.
+ *
+ * ctts_f0_targets: the reference's offline chain per utterance (one workgroup each): utils/pitch_tools.py:152-190 convert_continuos_f0 +
+ * log (start / end located BY VALUE like :171-172), preprocessor.py:612-618 get_f0cwt (np.mean / np.std, ddof 0, over the utterance's own
+ * frames), :193-209 get_lf0_cwt = real(cwt((cont_lf0 - mean) / std)) with pycwt's published definition for the Mexican hat at
+ * dt = 0.005, dj = 1, s0 = 0.01, J = 9: zero-pad to M = 2^ceil(log2 n), W_j = ifft(fft(x, M) sqrt(s_j w_1 M) psi(s_j w))[:n],
+ * psi(f) = f^2 exp(-f^2 / 2) / sqrt(Gamma(2.5)), s_j = s0 2^j, w = 2 pi fftfreq(M, dt).  M is the utterance's own power of two.
+ *   f0 [B,F] Hz (0 = unvoiced); frames [B] int32 (clamped to [0, F]); uv [B,F] = (f0 == 0) as 0 / 1 floats (the dataset's polarity,
+ *   norm_interp_f0); cont_lf0 [B,F]; mean_std [B,2]; cwt_spec [B,F,10]; valid [B] int32.  valid = 0 - and every output row of the
+ *   utterance 0 - when it has no voiced frame, when its cont_lf0 is constant (std == 0, decided exactly: max == min), or when any output
+ *   is not finite.  Frames at or beyond frames[b] are 0 in every output.  DOMAIN: 1 <= F <= 4096 (refused otherwise), nscale = 10.
+ * ctts_norm_interp_f0: the model-side f0 target (utils/pitch_tools.py:39-66 with pitch_norm "log", use_uv): log2(f0 + eps), 0 at
+ * unvoiced frames, then np.interp over the unvoiced positions (edge values held); all unvoiced -> zeros.  Same kernel, other mode. */
+size_t ctts_pitch_track_workspace_bytes(void);
+int ctts_pitch_track_prepare(float* workspace, void* stream);
+int ctts_pitch_track(const float* wav, const int32_t* lens, const float* workspace, float* peak, float* f0, float* strength, int B, int N,
+                     int sr, int hop, float f0_min, float f0_max, float voicing_threshold, float silence_threshold, void* stream);
+int ctts_f0_targets(const float* f0, const int32_t* frames, float* uv, float* cont_lf0, float* mean_std, float* cwt_spec, int32_t* valid,
+                    int B, int F, void* stream);
+int ctts_norm_interp_f0(const float* f0, const int32_t* frames, float* f0_norm, float* uv, int B, int F, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
