@@ -13,7 +13,11 @@ bottleneck.  Here:
   * `Prefetcher`                 - a background thread that collates, packs and uploads `depth` batches ahead; the consumer only
                                    waits on an event.
 
-No arithmetic happens here; the module is host plumbing (numpy + pinned memory + streams).
+No arithmetic happens here; the module is host plumbing (numpy + pinned memory + streams).  The one exception is opt-in:
+`attn_prior="device"` (reprocess / collate / PackedBatch.pack / Prefetcher) drops the per-utterance `attn_prior` files from the path -
+samples need no such field, position 18 of the tuple is None, and `to_device` fills `attn_priors` with the beta-binomial prior kernel
+(preprocess.attention_prior) from the uploaded `src_lens` / `mel_lens`, right after the copy and on the same stream, into a segment of
+the same device buffer.  The default, "files", is the reference's path, unchanged.
 """
 import queue
 import threading
@@ -40,8 +44,17 @@ def _pad_2d(xs):
     return out
 
 
-def reprocess(data, idxs, learn_alignment=False, pitch_cwt=True, load_spker_embed=False):
-    """`Dataset.reprocess` (dataset.py:166-228): gather the samples `idxs` of `data` and pad each field to the batch maximum."""
+def _prior_mode(attn_prior):
+    if attn_prior not in ("files", "device"):
+        raise ValueError(f"attn_prior {attn_prior!r}: expected 'files' or 'device'")
+    return attn_prior
+
+
+def reprocess(data, idxs, learn_alignment=False, pitch_cwt=True, load_spker_embed=False, attn_prior="files"):
+    """`Dataset.reprocess` (dataset.py:166-228): gather the samples `idxs` of `data` and pad each field to the batch maximum.
+    attn_prior="device" (with learn_alignment): the samples' `attn_prior` field is not read and position 18 is None - the prior is
+    computed on the device after the upload (`PackedBatch.pack(..., attn_prior="device")`)."""
+    _prior_mode(attn_prior)
     g = lambda k: [data[i][k] for i in idxs]                                     # noqa: E731
     texts, mels = g("text"), g("mel")
     text_lens = np.array([t.shape[0] for t in texts])
@@ -51,7 +64,9 @@ def reprocess(data, idxs, learn_alignment=False, pitch_cwt=True, load_spker_embe
         cwt_specs = _pad_2d(g("cwt_spec"))
         f0_means, f0_stds = np.array(g("f0_mean")), np.array(g("f0_std"))
     durations = mel2phs = attn_priors = None
-    if learn_alignment:
+    if learn_alignment and attn_prior == "device":
+        pass
+    elif learn_alignment:
         attn_priors = np.zeros((len(idxs), int(text_lens.max()), int(mel_lens.max())), dtype=np.float32)   # pad_3D, tools.py:570-574
         for i, a in enumerate(g("attn_prior")):
             attn_priors[i, :a.shape[0], :a.shape[1]] = a
@@ -85,14 +100,22 @@ _FIELDS = [("speakers", 2, np.int64), ("texts", 3, np.int64), ("src_lens", 4, No
 class PackedBatch:
     """One collated batch as a single pinned host buffer + layout table."""
 
-    def __init__(self, ids, raw_texts, max_src_len, max_mel_len, layout, host):
+    def __init__(self, ids, raw_texts, max_src_len, max_mel_len, layout, host, device_layout=None, prior_scaling_factor=None):
         self.ids, self.raw_texts = ids, raw_texts
         self.max_src_len, self.max_mel_len = int(max_src_len), int(max_mel_len)
         self.layout = layout                # name -> (byte offset, shape, torch dtype)
         self.host = host                    # uint8 tensor (pinned when CUDA is available)
+        self.device_layout = device_layout or {}      # segments that exist only in the device buffer (attn_prior="device"), behind the host's
+        self.prior_scaling_factor = prior_scaling_factor
+        self.device_bytes = max([host.numel()] + [o + int(np.prod(sh)) * torch.empty(0, dtype=dt).element_size()
+                                                  for o, sh, dt in self.device_layout.values()])
 
     @staticmethod
-    def pack(batch, pin=None):
+    def pack(batch, pin=None, attn_prior="files", scaling_factor=1.0):
+        """attn_prior="device": the batch carries no priors (position 18 is None); a float32 [B, max_src_len, max_mel_len] segment is
+        reserved behind the uploaded fields and `to_device` fills it on the device (beta-binomial prior, `scaling_factor`)."""
+        if _prior_mode(attn_prior) == "device" and batch[18] is not None:
+            raise ValueError("attn_prior='device' but the batch already carries attn_priors: collate it with attn_prior='device'")
         arrays, off = {}, 0
         for name, pos, dt in _FIELDS:
             a = batch[pos]
@@ -108,11 +131,16 @@ class PackedBatch:
         for name, (o, a) in arrays.items():
             hv[o:o + a.nbytes] = a.view(np.uint8).reshape(-1)
             layout[name] = (o, tuple(a.shape), torch.from_numpy(np.empty(0, dtype=a.dtype)).dtype)
-        return PackedBatch(batch[0], batch[1], batch[5], batch[8], layout, host)
+        device_layout = None
+        if attn_prior == "device":
+            device_layout = {"attn_priors": (off, (len(batch[4]), int(batch[5]), int(batch[8])), torch.float32)}
+        return PackedBatch(batch[0], batch[1], batch[5], batch[8], layout, host, device_layout,
+                           float(scaling_factor) if attn_prior == "device" else None)
 
     def _views(self, buf):
         out = {}
-        for name, (o, shape, dtype) in self.layout.items():
+        both = list(self.layout.items()) + (list(self.device_layout.items()) if buf.numel() >= self.device_bytes else [])
+        for name, (o, shape, dtype) in both:
             n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
             out[name] = buf[o:o + n].view(dtype).view(shape)
         return out
@@ -134,12 +162,16 @@ class PackedBatch:
             raise RuntimeError("PackedBatch.to_device targets the HIP device; use host_views() to inspect a batch on the host")
         stream = stream or torch.cuda.current_stream()
         with torch.cuda.stream(stream):
-            dev = torch.empty(self.host.numel(), dtype=torch.uint8, device=device)
-            dev.copy_(self.host, non_blocking=True)
+            dev = torch.empty(self.device_bytes, dtype=torch.uint8, device=device)
+            dev[:self.host.numel()].copy_(self.host, non_blocking=True)
+            views = self._views(dev)
+            if self.device_layout:
+                from .preprocess import attention_prior
+                attention_prior(views["src_lens"], views["mel_lens"], self.prior_scaling_factor, out=views["attn_priors"])
             ev = torch.cuda.Event()
             ev.record(stream)
         self.device_buffer = dev              # consumers on another stream must dev.record_stream(their stream) (Prefetcher does)
-        return self.as_reference_list(self._views(dev)), ev
+        return self.as_reference_list(views), ev
 
 
 class Prefetcher:
@@ -147,7 +179,8 @@ class Prefetcher:
     `batches`: iterable of 20-tuples (e.g. the lists `collate` returns).  Iterating yields reference-style 14-lists whose tensors
     are already resident; the consumer stream is made to wait on the copy event (no host sync)."""
 
-    def __init__(self, batches, device, depth=2):
+    def __init__(self, batches, device, depth=2, attn_prior="files", scaling_factor=1.0):
+        self.pack_kw = {"attn_prior": _prior_mode(attn_prior), "scaling_factor": scaling_factor}
         self.device = torch.device(device)
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -161,7 +194,7 @@ class Prefetcher:
         try:
             torch.cuda.set_device(self.device)
             for b in it:
-                pb = PackedBatch.pack(b)
+                pb = PackedBatch.pack(b, **self.pack_kw)
                 views, ev = pb.to_device(self.device, self.copy_stream)
                 self.q.put((views, ev, pb.device_buffer))
         except Exception as e:          # noqa: BLE001   (surface worker errors in the consumer)

@@ -1657,3 +1657,78 @@ def norm_interp_f0(f0, frames, eps=1e-9):
     uv = torch.empty_like(out)
     _lib.check(_lib.load().ctts_norm_interp_f0(_p(f0), _p(frames), _p(out), _p(uv), B, F, float(eps), _stream()), "ctts_norm_interp_f0")
     return out, uv
+
+
+# ---- dataset preparation: silence trim, alignment prior, outlier filter + moments (csrc/preprocess.hip) ---------------------------
+OUTLIER_MAX_VALUES = 4096
+
+
+def _lens_i32(lens, B, what):
+    if lens is None or not torch.is_tensor(lens) or _frames_arg(lens).numel() != B:
+        raise _lib.CttsError(f"{what}: lengths must be an int32 device tensor with one entry per utterance")
+    return lens
+
+
+def trim_silence(wav, lens, top_db, frame_length=1024, hop=256):
+    """wav [B,N] float32, lens int32 [B] samples -> (start int32 [B], end int32 [B], mse [B, 1 + N // hop] - the frame powers)"""
+    if not torch.is_tensor(wav) or wav.dim() != 2:
+        raise _lib.CttsError("trim_silence: expected wav [B, N]")
+    _p(wav)
+    _al4(_f32c(wav, "wav"), "wav")
+    B, N = wav.shape
+    if B < 1 or N < 1:
+        raise _lib.CttsError(f"trim_silence: empty batch {tuple(wav.shape)}")
+    _lens_i32(lens, B, "trim_silence")
+    if int(hop) < 1 or int(frame_length) < 2:
+        raise _lib.CttsError(f"trim_silence: need frame_length >= 2 and hop >= 1, got {frame_length} / {hop}")
+    lib = _lib.load()
+    mse = torch.empty(lib.ctts_trim_silence_workspace_bytes(B, N, int(hop)) // 4, dtype=torch.float32, device=wav.device)
+    start = torch.empty(B, dtype=torch.int32, device=wav.device)
+    end = torch.empty_like(start)
+    _lib.check(lib.ctts_trim_silence(_p(wav), _p(lens), _p(mse), _p(start), _p(end), B, N, float(top_db), int(frame_length), int(hop), _stream()),
+               "ctts_trim_silence")
+    return start, end, mse.view(B, 1 + N // int(hop))
+
+
+def attn_prior(src_lens, mel_lens, out, scaling_factor=1.0):
+    """src_lens, mel_lens int32 [B]; out float32 [B,Ts,Tm] view with a contiguous last dimension - written in place, every element"""
+    if not torch.is_tensor(out) or out.dim() != 3 or out.dtype != torch.float32:
+        raise _lib.CttsError("attn_prior: out must be a float32 [B, Ts, Tm] tensor")
+    _p(out)
+    _al4(out, "out")
+    B, Ts, Tm = out.shape
+    if B < 1 or Ts < 1 or Tm < 1:
+        raise _lib.CttsError(f"attn_prior: empty output {tuple(out.shape)}")
+    sb, ss, st = out.stride()
+    if st != 1 and Tm > 1:
+        raise _lib.CttsError("attn_prior: the last dimension of out must be contiguous")
+    if Ts == 1:
+        ss = max(ss, Tm)
+    if B == 1:
+        sb = max(sb, (Ts - 1) * ss + Tm)
+    _lens_i32(src_lens, B, "attn_prior")
+    _lens_i32(mel_lens, B, "attn_prior")
+    _lib.check(_lib.load().ctts_attn_prior(_p(src_lens), _p(mel_lens), _p(out), B, Ts, Tm, sb, ss, float(scaling_factor), _stream()), "ctts_attn_prior")
+    return out
+
+
+def outlier_stats(values, lens):
+    """values [B,L] float32, lens int32 [B] -> (keep uint8 [B,L], count int32 [B], sum float64 [B], m2 float64 [B], min [B], max [B])"""
+    if not torch.is_tensor(values) or values.dim() != 2:
+        raise _lib.CttsError("outlier_stats: expected values [B, L]")
+    _p(values)
+    _al4(_f32c(values, "values"), "values")
+    B, L = values.shape
+    if B < 1 or L < 1:
+        raise _lib.CttsError(f"outlier_stats: empty batch {tuple(values.shape)}")
+    _lens_i32(lens, B, "outlier_stats")
+    dev = values.device
+    keep = torch.empty(B, L, dtype=torch.uint8, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    s = torch.empty(B, dtype=torch.float64, device=dev)
+    m2 = torch.empty_like(s)
+    lo = torch.empty(B, dtype=torch.float32, device=dev)
+    hi = torch.empty_like(lo)
+    _lib.check(_lib.load().ctts_outlier_stats(_p(values), _p(lens), _p(keep), _p(count), _p(s), _p(m2), _p(lo), _p(hi), B, L, _stream()),
+               "ctts_outlier_stats")
+    return keep, count, s, m2, lo, hi

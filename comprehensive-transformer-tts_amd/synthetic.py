@@ -70,21 +70,31 @@ def to_device(batch, device):
             out[k] = {kk: (vv.to(device) if torch.is_tensor(vv) else vv) for kk, vv in v.items()}
         else:
             out[k] = v.to(device) if torch.is_tensor(v) else v
+    if out.get("prior_scaling_factor") is not None and out.get("attn_priors") is None:       # make_unsup_batch(prior="beta_binomial")
+        from .preprocess import attention_prior
+        out["attn_priors"] = attention_prior(out["src_lens"], out["mel_lens"], out["prior_scaling_factor"],
+                                             max_src_len=out["texts"].shape[1], max_mel_len=out["mels"].shape[1])
     return out
 
 
-def make_unsup_batch(src_lens=None, frames_per_phone=8, seed=1234, **kw):
+def make_unsup_batch(src_lens=None, frames_per_phone=8, seed=1234, prior="band", scaling_factor=1.0, **kw):
     """learn_alignment=True inputs: no duration targets, frame-level energy targets [B,Tm] and a positive
-    attention prior [B,Ts,Tm] (a smooth diagonal band standing in for the beta-binomial prior of preprocessor.py:551-560)."""
+    attention prior [B,Ts,Tm].  prior="band" (default): a smooth diagonal band standing in for the beta-binomial prior of
+    preprocessor.py:551-560; prior="beta_binomial": the real prior - the CPU batch carries `attn_priors` = None and
+    `prior_scaling_factor`, and `to_device` computes it on the device (preprocess.attention_prior).  Everything else is the same."""
+    if prior not in ("band", "beta_binomial"):
+        raise ValueError(f"prior {prior!r}: expected 'band' or 'beta_binomial'")
     b = make_batch(src_lens, frames_per_phone, seed=seed, **kw)
     g = torch.Generator().manual_seed(seed + 1)
     B, Ts, Tm = b["texts"].shape[0], b["texts"].shape[1], b["mels"].shape[1]
     P, M = b["src_lens"].float()[:, None, None], b["mel_lens"].float()[:, None, None]
     s_ = torch.arange(Ts)[None, :, None] / P
     t_ = torch.arange(Tm)[None, None, :] / M
-    prior = torch.exp(-((t_ - s_) ** 2) / 0.02) + 0.05 * torch.rand(B, Ts, Tm, generator=g)
+    band = torch.exp(-((t_ - s_) ** 2) / 0.02) + 0.05 * torch.rand(B, Ts, Tm, generator=g)
     valid = (torch.arange(Ts)[None, :, None] < P) & (torch.arange(Tm)[None, None, :] < M)
-    b["attn_priors"] = prior * valid
+    b["attn_priors"] = band * valid
+    if prior == "beta_binomial":
+        b["attn_priors"], b["prior_scaling_factor"] = None, float(scaling_factor)
     b["d_targets"] = None
     b["e_targets"] = torch.randn(B, Tm, generator=g) * (torch.arange(Tm)[None, :] < b["mel_lens"][:, None])
     return b
@@ -160,4 +170,6 @@ def shard(batch, rank, world, order="strided"):
     }
     if batch.get("attn_priors") is not None:
         out["attn_priors"] = cut(batch["attn_priors"], [(1, Ts), (2, Tm)])
+    if batch.get("prior_scaling_factor") is not None:
+        out["prior_scaling_factor"] = batch["prior_scaling_factor"]
     return out

@@ -763,6 +763,45 @@ int ctts_f0_targets(const float* f0, const int32_t* frames, float* uv, float* co
                     int B, int F, void* stream);
 int ctts_norm_interp_f0(const float* f0, const int32_t* frames, float* f0_norm, float* uv, int B, int F, float eps, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Dataset preparation on the device (csrc/preprocess.hip): the three host steps of the reference's
+ * preprocessor/preprocessor.py - silence trim (:363-368), beta-binomial alignment prior (:551-560), outlier filter and the moments of
+ * the normalisation statistics (:620-628, StandardScaler.partial_fit).  fp32 data, lengths are int32 device arrays and are clamped to
+ * the padded width in the kernels; stream-ordered, no allocation, no host sync, no float atomics: bit-reproducible run to run, and an
+ * utterance's result does not depend on the batch around it.
+ *
+ * ctts_trim_silence: librosa 0.7.2 effects.trim with ref = np.max, restated (PARITY UNPINNED: librosa is not installed where this
+ * project is built).  wav [B,N], lens [B] samples.  The utterance's own lens[b] samples are reflect-padded by frame_length / 2 on each
+ * side; frames f = 0 .. lens[b] / hop; mse_f = mean of squares of padded samples [f hop, f hop + frame_length), accumulated in double;
+ * ref = max_f mse_f; frame f is non-silent iff 10 log10(max(1e-10, mse_f)) - 10 log10(max(1e-10, ref)) > -top_db (evaluated in double);
+ * start[b] = hop first, end[b] = min(lens[b], hop (last + 1)); no non-silent frame (or lens[b] <= 0) gives start = end = 0.  Digital
+ * silence has mse_f = ref = 0, so every frame is 0 dB below the reference: nothing is trimmed, as in librosa.
+ *   Samples at or beyond lens[b] are never read.  DOMAIN: lens[b] > frame_length / 2 (reflection); a shorter device-given length has
+ *   its reflected indices clamped into [0, lens[b]) - memory-safe, not librosa's answer.  frame_length >= 2, hop >= 1, B <= 65535.
+ *   workspace: ctts_trim_silence_workspace_bytes(B, N, hop) bytes; after the call it holds mse as float [B][1 + N / hop] (frames at or
+ *   beyond 1 + lens[b] / hop are 0), each within one float rounding of the double evaluation.
+ *
+ * ctts_attn_prior: out[b][s][t] = BetaBinom.pmf(t; n = mel_lens[b], a = sf (s + 1), b = sf (src_lens[b] - s)) for s < src_lens[b] and
+ * t < mel_lens[b], 0 elsewhere (the zero padding of pad_3D / data.reprocess) - EVERY element of the [B,Ts,Tm] view is written.  The
+ * reference calls its function with the two counts swapped against the parameter names (:409-413 vs :551), which is what this states:
+ * n is the mel length, rows run over phonemes, the support point t = n is never emitted and rows do not sum to 1.  Evaluated in double
+ * through lgamma, rounded once to float.  out is a view: element (b, s, t) lives at out[b stride_b + s stride_s + t] (strides in
+ * floats, stride_s >= Tm, stride_b >= (Ts - 1) stride_s + Tm).  scaling_factor > 0, B <= 65535.
+ *
+ * ctts_outlier_stats: per utterance b over values[b][0 .. lens[b]): p25 / p75 = numpy's default (linear) percentile of the sorted
+ * values (position q (n - 1), interpolated between the neighbours, in double); keep[b][i] = 1 iff p25 - 1.5 IQR < v < p75 + 1.5 IQR
+ * (strict: a constant utterance and n = 1 keep nothing), 0 for i >= lens[b]; count[b], sum[b] and m2[b] = sum (v - sum / count)^2
+ * over the kept values in double (two passes), vmin[b] / vmax[b] over the kept values (+inf / -inf when none is kept).
+ * The dataset mean / std is the Chan merge of the (count, sum, m2) triples in utterance order = StandardScaler.partial_fit fed one
+ * utterance at a time (ctts_amd.preprocess.merge_moments).  DOMAIN: 1 <= L <= 4096 (sorted in LDS; refused otherwise, never truncated). */
+size_t ctts_trim_silence_workspace_bytes(int B, int N, int hop);
+int ctts_trim_silence(const float* wav, const int32_t* lens, float* workspace, int32_t* start, int32_t* end, int B, int N, float top_db,
+                      int frame_length, int hop, void* stream);
+int ctts_attn_prior(const int32_t* src_lens, const int32_t* mel_lens, float* out, int B, int Ts, int Tm, int64_t stride_b, int64_t stride_s,
+                    float scaling_factor, void* stream);
+int ctts_outlier_stats(const float* values, const int32_t* lens, uint8_t* keep, int32_t* count, double* sum, double* m2, float* vmin,
+                       float* vmax, int B, int L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
