@@ -48,6 +48,16 @@ class GemmDesc(C.Structure):
     ]
 
 
+class GemmRouteInfo(C.Structure):
+    """ctts_gemm_route_info of include/ctts.h"""
+    _fields_ = [("kind", _i32), ("tile_m", _i32), ("tile_n", _i32), ("split_k", _i32), ("k_granule", _i32)]
+
+
+# enum ctts_gemm_kind of include/ctts.h, in its order
+GEMM_KINDS = ("none", "planes", "planes_wgrad", "weight_stationary", "x6", "stream_k", "x6tn", "scalar64", "buf128", "buf_k2", "buf_narrow",
+              "buf64", "vec128", "vec64")
+
+
 class VconvDesc(C.Structure):
     """ctts_vconv_desc of include/ctts.h (ctypes zero-initialises it)"""
     _fields_ = [
@@ -101,6 +111,7 @@ class RepackTask(C.Structure):
 _SIGNATURES = {
     "ctts_conv_dgrad_weights": [C.POINTER(RepackTask), C.c_int, _vp],
     "ctts_gemm_split_plan": [C.POINTER(GemmDesc), C.POINTER(_i32), C.POINTER(_i64)],
+    "ctts_gemm_route": [C.POINTER(GemmDesc), C.POINTER(GemmRouteInfo)],
     "ctts_partial_sums": [C.POINTER(PsumTask), C.c_int, _vp],
     "ctts_reduce_parts": [C.c_int, _i64, C.c_int],
     "ctts_xcd_probe": [_vp, C.c_int, _vp],
@@ -212,6 +223,7 @@ EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["ctts_last_error", "ctts_version"
                                                "ctts_griffinlim_workspace_bytes", "ctts_griffinlim_state_floats",
                                                "ctts_pitch_track_workspace_bytes", "ctts_trim_silence_workspace_bytes"])
 ADAM_STATE_FLOATS = 3 + 2048          # CTTS_ADAM_STATE_FLOATS of include/ctts.h
+ABI_VERSION = 2                       # ctts_version() of the library this binding was written for
 
 _lib = None
 
@@ -231,14 +243,17 @@ def load():
             "(or __graft_entry__.build()).  There is no CPU / PyTorch fallback for the hot path."
         )
     lib = C.CDLL(LIB_PATH)
+    lib.ctts_version.restype = C.c_int
+    lib.ctts_version.argtypes = []
+    if lib.ctts_version() != ABI_VERSION:      # a stale build fails here, not inside a kernel that reads a descriptor laid out differently
+        raise CttsError(f"{LIB_PATH} has ABI version {lib.ctts_version()}, this package needs {ABI_VERSION} - rebuild it with "
+                        "comprehensive-transformer-tts_amd/csrc/build.sh (or __graft_entry__.build())")
     for name, argtypes in _SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int
     lib.ctts_last_error.restype = C.c_char_p
     lib.ctts_last_error.argtypes = []
-    lib.ctts_version.restype = C.c_int
-    lib.ctts_version.argtypes = []
     lib.ctts_mha_supported.restype = C.c_int
     lib.ctts_mha_supported.argtypes = [C.c_int, C.c_int]
     lib.ctts_mel_spectrogram_workspace_bytes.restype = C.c_size_t

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "../../include/ctts.h"
 
 #define CTTS_WAVE 64
@@ -12,6 +13,12 @@ void ctts_set_error(const char* fmt, ...);
 // a hipGraph re-execute incorrectly on this ROCm stack (from the second replay on, bytes 8..11 of the buffer keep stale data - measured
 // with tools/check_graph_memset.py), which silently corrupts accumulators when a train step is replayed.
 int ctts_zero_async(void* p, size_t bytes, hipStream_t st);
+
+// an integer tuning knob from the environment (host side; callers read theirs once, into a function-local static)
+static inline int ctts_env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
 
 #define CTTS_CHECK_LAUNCH(name)                                                     \
   do {                                                                              \

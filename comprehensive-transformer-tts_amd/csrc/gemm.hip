@@ -12,6 +12,7 @@
 #include "ctts_common.h"
 #include "gemm_common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -1143,13 +1144,25 @@ int launch_buf_k2(const ctts_gemm_desc& d, hipStream_t st) {
   return 0;
 }
 
-int dispatch_buf_k2(const ctts_gemm_desc& d, hipStream_t st) {
-  const bool conv = d.conv_T > 0;
-  if (d.a_kc && d.b_kc) return conv ? launch_buf_k2<true, true, true>(d, st) : launch_buf_k2<true, true, false>(d, st);
-  if (d.a_kc && !d.b_kc) return conv ? launch_buf_k2<true, false, true>(d, st) : launch_buf_k2<true, false, false>(d, st);
-  if (!d.a_kc && !d.b_kc) return conv ? launch_buf_k2<false, false, true>(d, st) : launch_buf_k2<false, false, false>(d, st);
+// The three instantiated operand layouts (NT, NN, TN), with or without a conv view: f(a_kc, b_kc, conv) gets them as compile-time
+// constants.  WITH_CONV = false: the caller has no conv instantiations (its route never carries a conv view).
+template <bool WITH_CONV, class F>
+int for_layout(const ctts_gemm_desc& d, F f) {
+  auto go = [&](auto a, auto b) {
+    if constexpr (WITH_CONV) {
+      if (d.conv_T > 0) return f(a, b, std::true_type{});
+    }
+    return f(a, b, std::false_type{});
+  };
+  if (d.a_kc && d.b_kc) return go(std::true_type{}, std::true_type{});
+  if (d.a_kc && !d.b_kc) return go(std::true_type{}, std::false_type{});
+  if (!d.a_kc && !d.b_kc) return go(std::false_type{}, std::false_type{});
   ctts_set_error("ctts_gemm: layout a_kc=0,b_kc=1 is not instantiated");
   return -1;
+}
+
+int dispatch_buf_k2(const ctts_gemm_desc& d, hipStream_t st) {
+  return for_layout<true>(d, [&](auto a, auto b, auto c) { return launch_buf_k2<a(), b(), c()>(d, st); });
 }
 
 template <int BM, int BN, bool A_KC, bool B_KC, bool CONV>
@@ -1171,25 +1184,11 @@ int launch_buf(const ctts_gemm_desc& d, hipStream_t st) {
   return 0;
 }
 
-template <int BM, int BN>
-int dispatch_buf(const ctts_gemm_desc& d, hipStream_t st) {
-  const bool conv = d.conv_T > 0;
-  if (d.a_kc && d.b_kc) return conv ? launch_buf<BM, BN, true, true, true>(d, st) : launch_buf<BM, BN, true, true, false>(d, st);
-  if (d.a_kc && !d.b_kc) return conv ? launch_buf<BM, BN, true, false, true>(d, st) : launch_buf<BM, BN, true, false, false>(d, st);
-  if (!d.a_kc && !d.b_kc) return conv ? launch_buf<BM, BN, false, false, true>(d, st) : launch_buf<BM, BN, false, false, false>(d, st);
-  ctts_set_error("ctts_gemm: layout a_kc=0,b_kc=1 is not instantiated");
-  return -1;
-}
-
 // 128 x 32 tiles (4 x 1 waves) for outputs at most 32 columns wide: with 64 x 64 tiles half of every workgroup's MFMAs would multiply
 // zero columns.  The three products of the conformer's attention backward that consume dS ([T, 32] = [T, T] x [T, 32] per (b, h),
 // ctts_relmha_bwd) are the users.  No conv views.
 int dispatch_buf_narrow(const ctts_gemm_desc& d, hipStream_t st) {
-  if (d.a_kc && d.b_kc) return launch_buf<128, 32, true, true, false>(d, st);
-  if (d.a_kc && !d.b_kc) return launch_buf<128, 32, true, false, false>(d, st);
-  if (!d.a_kc && !d.b_kc) return launch_buf<128, 32, false, false, false>(d, st);
-  ctts_set_error("ctts_gemm: layout a_kc=0,b_kc=1 is not instantiated");
-  return -1;
+  return for_layout<false>(d, [&](auto a, auto b, auto c) { return launch_buf<128, 32, a(), b(), c()>(d, st); });
 }
 
 // buffer loaders need: no per-batch length limits and every operand element within 2 GiB of its (batch) base
@@ -1198,16 +1197,6 @@ bool buf_ok(const ctts_gemm_desc& d) {
   const long a_ext = d.a_kc ? ((long)d.M * d.lda + d.K) : ((long)d.K * d.lda + d.M);
   const long b_ext = d.b_kc ? ((long)d.N * d.ldb + d.K) : ((long)d.K * d.ldb + d.N);
   return a_ext * 4 < 0x7FFF0000L && b_ext * 4 < 0x7FFF0000L;
-}
-
-template <int BM, int BN, bool VEC>
-int dispatch_layout(const ctts_gemm_desc& d, hipStream_t st) {
-  const bool conv = d.conv_T > 0;
-  if (d.a_kc && d.b_kc) return conv ? launch<BM, BN, true, true, true, VEC>(d, st) : launch<BM, BN, true, true, false, VEC>(d, st);
-  if (d.a_kc && !d.b_kc) return conv ? launch<BM, BN, true, false, true, VEC>(d, st) : launch<BM, BN, true, false, false, VEC>(d, st);
-  if (!d.a_kc && !d.b_kc) return conv ? launch<BM, BN, false, false, true, VEC>(d, st) : launch<BM, BN, false, false, false, VEC>(d, st);
-  ctts_set_error("ctts_gemm: layout a_kc=0,b_kc=1 is not instantiated");
-  return -1;
 }
 
 // eligibility of the branch-free 16-byte loaders (see VLoaderKC)
@@ -1328,15 +1317,12 @@ extern "C" int ctts_row_tile_map(const int32_t* row_lens, int row_T, int row_hal
   return 0;
 }
 
-namespace {
-struct GemmSplitPlan { int deferred_ok; int count; long stride; };
-}
-// plan != nullptr: no launch - only answer how a split-K launch of this descriptor would lay out its partial matrices
-// fp32-on-bf16-pipe kernel (gemm_x6_kernel): large unbatched NT launches whose N is a multiple of the 128-column tile.  The arithmetic is
-// the CALLER's choice, per descriptor (ctts_gemm_desc.bf16_split: 0 = fp32 MFMA only, 1 = allowed, 2 = allowed below the size thresholds).
-static bool gemm_x6_takes(const ctts_gemm_desc& d) {
+// ---- fp32-on-bf16-pipe kernels of this file (the CALLER chooses the arithmetic, per descriptor - ctts_gemm_desc.bf16_split: 0 = fp32
+// MFMA only, 1 = allowed, 2 = allowed below the size thresholds).  gemm_x6_kernel: large unbatched NT launches whose N is a multiple of
+// the 128-column tile.
+static bool x6_plan(const ctts_gemm_desc& d) {
   const int on = d.bf16_split;
-  static const long min_tiles = getenv("CTTS_X6_MIN_TILES") ? atol(getenv("CTTS_X6_MIN_TILES")) : 384;
+  static const long min_tiles = ctts_env_int("CTTS_X6_MIN_TILES", 384);
   if (on < 1 || !d.a_kc || !d.b_kc || d.nb0 * d.nb1 != 1 || d.split_k > 1 || d.E || d.lens || d.conv_on_b) return false;
   if (d.K < 256 || d.K % BK || d.N % 128 || d.M < 1024) return false;
   if (d.conv_T > 0 && d.conv_cin % 4) return false;
@@ -1345,9 +1331,9 @@ static bool gemm_x6_takes(const ctts_gemm_desc& d) {
 }
 
 // the TN (weight-gradient) form: unbatched, both operands reduction-major, tile-aligned output, long reduction; CTTS_X6_TN=0 turns it off
-static bool gemm_x6tn_takes(const ctts_gemm_desc& d) {
-  static const int tn = getenv("CTTS_X6_TN") ? atoi(getenv("CTTS_X6_TN")) : 1;
-  static const long min_wg = getenv("CTTS_X6_TN_MIN_WG") ? atol(getenv("CTTS_X6_TN_MIN_WG")) : 384;
+static bool x6tn_plan(const ctts_gemm_desc& d) {
+  static const int tn = ctts_env_int("CTTS_X6_TN", 1);
+  static const long min_wg = ctts_env_int("CTTS_X6_TN_MIN_WG", 384);
   if (d.bf16_split < 1 || !tn || d.a_kc || d.b_kc || d.nb0 * d.nb1 != 1 || d.E || d.lens || d.epi_bwd) return false;
   if (d.M % 128 || d.N % 128 || d.K % BK || d.K < 2048) return false;
   // (a thread stages 8 consecutive reduction rows starting at a multiple of 8: they stay inside one utterance when conv_T % 8 == 0)
@@ -1356,7 +1342,7 @@ static bool gemm_x6tn_takes(const ctts_gemm_desc& d) {
   return vec_ok(d) && buf_ok(d);
 }
 
-static int gemm_x6tn_launch(const ctts_gemm_desc& d, hipStream_t st) {
+static int x6tn_launch(const ctts_gemm_desc& d, hipStream_t st) {
   const dim3 grid((d.M / 128) * (d.N / 128), d.split_k > 1 ? d.split_k : 1, 1);
   if (d.conv_T > 0) hipLaunchKernelGGL(gemm_x6tn_kernel<true>, grid, dim3(256), 0, st, d);
   else hipLaunchKernelGGL(gemm_x6tn_kernel<false>, grid, dim3(256), 0, st, d);
@@ -1364,7 +1350,7 @@ static int gemm_x6tn_launch(const ctts_gemm_desc& d, hipStream_t st) {
   return 0;
 }
 
-static int gemm_x6_launch(const ctts_gemm_desc& d, hipStream_t st) {
+static int x6_launch(const ctts_gemm_desc& d, hipStream_t st) {
   const int tiles = ((d.M + 127) / 128) * (d.N / 128);
   if (d.conv_T > 0) hipLaunchKernelGGL(gemm_x6_kernel<true>, dim3(tiles), dim3(256), 0, st, d);
   else hipLaunchKernelGGL(gemm_x6_kernel<false>, dim3(tiles), dim3(256), 0, st, d);
@@ -1372,70 +1358,38 @@ static int gemm_x6_launch(const ctts_gemm_desc& d, hipStream_t st) {
   return 0;
 }
 
-extern "C" int ctts_gemm_takes_bf16_split(const ctts_gemm_desc* dp) {
-  if (!dp) return 0;
-  ctts_gemm_desc d = *dp;
-  if (d.nb0 < 1) d.nb0 = 1;
-  if (d.nb1 < 1) d.nb1 = 1;
-  if (ctts_gemm_takes_planes(&d)) return 0;                  // ctts_gemm asks the plane kernel first,
-  if (ctts_gemm_takes_weight_stationary(&d)) return 0;       // then the weight-stationary kernel
-  return (gemm_x6_takes(d) || gemm_x6tn_takes(d)) ? 1 : 0;
-}
+// What gemm_route decides for one descriptor: the launch, the queries and the split plan all read this and nothing else.
+struct GemmRoute {
+  // kind; workgroup tile; split_k = K ranges that write partial matrices (the caller's, lowered until they fit; 1: none);
+  // k_granule = the K granularity of a split (the kernel's `chunk`)
+  ctts_gemm_route_info info;
+  bool split_fits;           // false: not even two partial matrices fit (an error for a launch)
+  int tile_group_n;          // descriptor adjustments of a tile-kernel launch: ctts_gemm_desc.tile_group_n ...
+  bool natural_order;        // ... and the tile_map == 1 sentinel (plain blockIdx order)
+  union { PlArgs pl; PlwArgs plw; WsArgs ws; SkArgs sk; };      // the planned arguments of the family that takes the launch
+  GemmGrid grid;
+};
 
-static int gemm_impl(const ctts_gemm_desc* dp, void* stream, GemmSplitPlan* plan) {
-  CTTS_REQUIRE(dp != nullptr, "ctts_gemm: null descriptor");
-  ctts_gemm_desc d = *dp;
-  CTTS_REQUIRE(d.A && d.B && d.C, "ctts_gemm: null operand pointer");
-  CTTS_REQUIRE(d.M >= 0 && d.N >= 0 && d.K >= 0, "ctts_gemm: negative dimension");
-  if (d.M == 0 || d.N == 0) return 0;
-  if (d.nb0 < 1) d.nb0 = 1;
-  if (d.nb1 < 1) d.nb1 = 1;
-  if (d.conv_T > 0) {
-    CTTS_REQUIRE(d.conv_cin > 0 && (d.conv_cin % 4) == 0, "ctts_gemm: conv view needs cin %% 4 == 0 (got %d)", d.conv_cin);
-    CTTS_REQUIRE(d.conv_on_b ? (!d.a_kc && !d.b_kc) : (d.a_kc != 0), "ctts_gemm: conv view on an unsupported operand layout");
-  }
-  CTTS_REQUIRE(d.p_drop >= 0.f && d.p_drop < 1.f, "ctts_gemm: p_drop out of range");
-  CTTS_REQUIRE(!d.epi_bwd || (d.split_k <= 1 && !d.bias && !d.R && !d.rowscale && !d.E && (!d.act || d.Z)),
-               "ctts_gemm: epi_bwd excludes bias, residual, rowscale, E and split-K, and needs Z when an activation is given");
-  CTTS_REQUIRE(!d.E || (d.rowsub && d.split_k <= 1 && !d.bias && !d.act && d.p_drop == 0.f && !d.R && !d.rowscale && !d.Z),
-               "ctts_gemm: the E/rowsub epilogue excludes bias, activation, dropout, residual, rowscale and split-K");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool x6tn = gemm_x6tn_takes(d);            // weight gradient on the bf16-split kernel: a tile-kernel launch with ordered split-K partials
-  if (plan) {
-    plan->deferred_ok = 0;
-    if (d.split_k <= 1 || ctts_gemm_plw_takes(d) || ctts_gemm_takes_weight_stationary(&d) || (!x6tn && ctts_gemm_takes_persistent(&d))) return 0;
-  } else {
-    const int pl = ctts_gemm_pl_try(d, st);      // pre-split bf16 planes given and eligible: persistent plane kernel (gemm_pl.hip)
-    if (pl != 0) return pl > 0 ? 0 : pl;
-    const int plw = ctts_gemm_plw_try(d, st);    // ... in the weight-gradient layout (gemm_plw.hip): adds into C itself, no partial matrices
-    if (plw != 0) return plw > 0 ? 0 : plw;
-    const int ws = ctts_gemm_ws_try(d, st);      // weight-stationary kernel (gemm_ws.hip) for K = 256 linears with many rows
-    if (ws != 0) return ws > 0 ? 0 : ws;
-    if (gemm_x6_takes(d)) return gemm_x6_launch(d, st);      // fp32 products on the bf16 matrix pipe (six-term split)
-    if (!x6tn) {
-      const int sk = ctts_gemm_sk_try(d, st);    // persistent stream-K kernel (gemm_sk.hip) when the descriptor is eligible
-      if (sk != 0) return sk > 0 ? 0 : sk;
-    }
-  }
+// The tile-per-workgroup kernels of this file: which one, its tile, and the order it walks its tiles in.  x6tn: x6tn_plan(d).
+static void tile_plan(const ctts_gemm_desc& d, bool x6tn, GemmRoute& r) {
   const long tiles128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128) * (d.split_k > 1 ? d.split_k : 1) * d.nb0 * d.nb1;
-  static const int force_tile = getenv("CTTS_FORCE_TILE") ? atoi(getenv("CTTS_FORCE_TILE")) : 0;   // tuning knob
+  static const int force_tile = ctts_env_int("CTTS_FORCE_TILE", 0);   // tuning knob
   static const bool natural = getenv("CTTS_NATURAL_ORDER") != nullptr;
   // XCD-grouped order for scheduled launches: default 4 n-groups (XCD x: n-group x % 4, every second scheduled m-tile) - halves the
   // L2-miss traffic of the FFN conv (FETCH_SIZE 441 -> 195 MB per launch) at unchanged time; CTTS_TILE_GROUP=<g> overrides, 0 = off.
-  static const int tile_group = getenv("CTTS_TILE_GROUP") ? atoi(getenv("CTTS_TILE_GROUP")) : -1;
-  d.tile_group_n = 0;
+  static const int tile_group = ctts_env_int("CTTS_TILE_GROUP", -1);
   if (tile_group != 0 && d.tile_map && d.tile_map != reinterpret_cast<const int32_t*>(1)) {
     const int tn = (d.N + 63) / 64, tmn = (d.M + 63) / 64;
     const int g = tile_group > 0 ? tile_group : ((tn >= 8 && tn % 4 == 0) ? tn / 4 : 0);
     if (g > 0 && tn % g == 0) {
       const int ng = tn / g;
-      if ((ng == 1 || ng == 2 || ng == 4 || ng == 8) && tmn % (8 / ng) == 0 && ((long)tmn * tn) % 8 == 0) d.tile_group_n = g;
+      if ((ng == 1 || ng == 2 || ng == 4 || ng == 8) && tmn % (8 / ng) == 0 && ((long)tmn * tn) % 8 == 0) r.tile_group_n = g;
     }
   }
   // CTTS_TN_NATURAL: plain blockIdx order for the weight-gradient (TN, split-K) launches only.  4-12 % faster in the isolated
   // micro-benchmark (96.6 -> 86 us FFN linear, 711 -> 683 us FFN conv) - in-step effect measured separately, off by default.
   static const bool tn_natural = getenv("CTTS_TN_NATURAL") != nullptr;
-  if ((natural || (tn_natural && !d.a_kc && !d.b_kc)) && !d.tile_map) d.tile_map = reinterpret_cast<const int32_t*>(1);
+  r.natural_order = (natural || (tn_natural && !d.a_kc && !d.b_kc)) && !d.tile_map;
   // 16-byte BUFFER loads only need dword-aligned addresses (the LDS side of the tile is aligned by construction), so the buffer kernels
   // also take operands whose base / leading dimension is not a multiple of 4 floats - the padded views (rows of T+1) of the relative
   // attention score slabs - as long as the chunking fits.  Pointer-based 16-byte loads (the non-buffer VEC path) need full alignment.
@@ -1445,11 +1399,9 @@ static int gemm_impl(const ctts_gemm_desc* dp, void* stream, GemmSplitPlan* plan
 #else
   const bool buf_unaligned = !aligned && chunks_ok(d) && d.conv_T <= 0 && !(d.lens && (d.lim_m || d.lim_n || d.lim_k));
 #endif
-  // ---- which kernel family / tile takes the launch (decided first: the ordered split-K sum needs the tile shape)
-  enum { K_SCALAR64, K_BUF128, K_BUF_K2, K_BUF_NARROW, K_BUF64, K_VEC128, K_VEC64, K_X6TN } kind;
-  int BMs = 64, BNs = 64;
-  if (x6tn) { kind = K_X6TN; BMs = BNs = 128; }
-  else if (!aligned && !(buf_unaligned && buf_ok(d))) kind = K_SCALAR64;
+  r.info.tile_m = r.info.tile_n = 64;
+  if (x6tn) { r.info.kind = CTTS_GEMM_X6TN; r.info.tile_m = r.info.tile_n = 128; }      // weight gradient on the bf16-split kernel, with ordered split-K partials like the others
+  else if (!aligned && !(buf_unaligned && buf_ok(d))) r.info.kind = CTTS_GEMM_SCALAR64;
 #ifndef CTTS_NO_BUF
   else if (buf_ok(d)) {
     // 64x64 tiles (64 VGPRs: 8 waves/SIMD) match the 128x128 kernel on every measured shape (109 / 119 / 108 / 107 TFLOP/s on FFN conv fwd,
@@ -1458,92 +1410,173 @@ static int gemm_impl(const ctts_gemm_desc* dp, void* stream, GemmSplitPlan* plan
     // under-filled forward / data-gradient launches (A K-contiguous, unbatched): few 64 x 64 tiles - the phoneme-level layers (2,048
     // rows).  Routing by the step time (same box): tile limit 160 / 320 / 640 / 1024: fs2 23.36 / 23.27 / 23.17 / 23.24 ms from 23.48,
     // conformer 27.78 / 27.84 / 27.62 / 27.90 from 28.14; K >= 256 instead of 512: another -0.03 / -0.05 ms.
-    static const int k2 = getenv("CTTS_K2_TILE") ? atoi(getenv("CTTS_K2_TILE")) : 640;          // largest 64 x 64 tile count routed here (0 = off)
-    static const int k2_mink = getenv("CTTS_K2_MIN_K") ? atoi(getenv("CTTS_K2_MIN_K")) : 256;
+    static const int k2 = ctts_env_int("CTTS_K2_TILE", 640);          // largest 64 x 64 tile count routed here (0 = off)
+    static const int k2_mink = ctts_env_int("CTTS_K2_MIN_K", 256);
     // the split-K weight gradients (TN) of those layers as well: conformer 27.82 -> 27.53 ms.  NOTE: the two-group kernel has no K-block
     // skipping (row_lens / tile_map are ignored for TN launches) - correct because the rows of dZ beyond a sequence's length are exactly
     // zero (every producer of a gradient masks or zero-fills its padded rows), it merely multiplies those zeros.
-    static const int k2_tn = getenv("CTTS_K2_TN") ? atoi(getenv("CTTS_K2_TN")) : 1;
-    static const bool narrow = getenv("CTTS_NARROW_TILE") ? atoi(getenv("CTTS_NARROW_TILE")) != 0 : true;
-    if (force_tile == 128) { kind = K_BUF128; BMs = BNs = 128; }
+    static const int k2_tn = ctts_env_int("CTTS_K2_TN", 1);
+    static const bool narrow = ctts_env_int("CTTS_NARROW_TILE", 1) != 0;
+    if (force_tile == 128) { r.info.kind = CTTS_GEMM_BUF128; r.info.tile_m = r.info.tile_n = 128; }
     else if (k2 && (d.a_kc || (k2_tn && !d.b_kc)) && d.nb0 * d.nb1 == 1 && !d.lens && d.N >= 64 && d.M >= 256 && d.K >= k2_mink &&
-             (long)((d.M + 63) / 64) * ((d.N + 63) / 64) * (d.split_k > 1 ? d.split_k : 1) <= k2) { kind = K_BUF_K2; BMs = 32; }
-    else if (narrow && d.N <= 32 && d.M >= 256 && d.conv_T <= 0 && !d.tile_map && !d.row_lens) { kind = K_BUF_NARROW; BMs = 128; BNs = 32; }
-    else kind = K_BUF64;
+             (long)((d.M + 63) / 64) * ((d.N + 63) / 64) * (d.split_k > 1 ? d.split_k : 1) <= k2) { r.info.kind = CTTS_GEMM_BUF_K2; r.info.tile_m = 32; }
+    else if (narrow && d.N <= 32 && d.M >= 256 && d.conv_T <= 0 && !d.tile_map && !r.natural_order && !d.row_lens) { r.info.kind = CTTS_GEMM_BUF_NARROW; r.info.tile_m = 128; r.info.tile_n = 32; }
+    else r.info.kind = CTTS_GEMM_BUF64;
   }
 #endif
   // weight-gradient (TN) reductions measured faster on 64x64 tiles (64 VGPRs: 8 waves/SIMD): 92.6 vs 84.6 TFLOP/s on the FFN conv wgrad
-  else if (tiles128 >= 256 && d.N > 64 && (d.a_kc || d.b_kc)) { kind = K_VEC128; BMs = BNs = 128; }
-  else kind = K_VEC64;
+  else if (tiles128 >= 256 && d.N > 64 && (d.a_kc || d.b_kc)) { r.info.kind = CTTS_GEMM_VEC128; r.info.tile_m = r.info.tile_n = 128; }
+  else r.info.kind = CTTS_GEMM_VEC64;
+  r.info.k_granule = r.info.kind == CTTS_GEMM_BUF_K2 ? 2 * BK : BK;
+}
 
+// THE order in which the kernel families are asked for a descriptor (nb0 / nb1 >= 1).  Pure: no launch, no error.  Tile kernels finish
+// split_k > 1 as an ordered split-K (gemm_common.h; splitk_reduce_kernel above): one partial matrix [M, N] per (batch, split) - in the
+// workspace, or in split_out when the caller keeps them and adds them itself later (ctts_partial_sums, many GEMMs per launch: no reduce
+// launch).  split_k is an upper bound, lowered until the partials fit (never below 2 - "C += alpha A B" is what split_k > 1 means);
+// unbounded_room: the split plan, whose caller sizes split_out from the answer.
+static void gemm_route(const ctts_gemm_desc& d, GemmRoute& r, bool unbounded_room = false) {
+  r.info = ctts_gemm_route_info{CTTS_GEMM_NONE, 128, 128, 1, 32};
+  r.split_fits = true;
+  r.tile_group_n = 0;
+  r.natural_order = false;
+  bool x6tn = false;
+  if (ctts_gemm_pl_plan(d, r.pl, r.grid)) r.info.kind = CTTS_GEMM_PLANES;                  // pre-split bf16 planes given and eligible: persistent plane kernel
+  else if (ctts_gemm_plw_plan(d, r.plw, r.grid)) r.info.kind = CTTS_GEMM_PLANES_WGRAD;     // ... in the weight-gradient layout: adds into C itself, no partial matrices
+  else if (ctts_gemm_ws_plan(d, r.ws, r.grid)) r.info.kind = CTTS_GEMM_WEIGHT_STATIONARY;  // K = 256 linears with many rows
+  else if (x6_plan(d)) { r.info.kind = CTTS_GEMM_X6; return; }                             // fp32 products on the bf16 matrix pipe (six-term split), 128 x 128 tiles
+  else if (!(x6tn = x6tn_plan(d)) && ctts_gemm_sk_plan(d, r.sk, r.grid)) r.info.kind = CTTS_GEMM_STREAM_K;      // (x6's weight-gradient form goes before stream-K)
+  if (r.info.kind != CTTS_GEMM_NONE) { r.info.tile_m = r.grid.tile_m; r.info.tile_n = r.grid.tile_n; return; }
+  tile_plan(d, x6tn, r);
   if (d.split_k > 1) {
-    // Ordered split-K (gemm_common.h; splitk_reduce_kernel above): one partial matrix [M, N] per (batch, split) in the
-    // caller's workspace.  split_k is an upper bound: it is lowered until the partials fit (never below 2 - "C += alpha A B" is what
-    // split_k > 1 means).
-    CTTS_REQUIRE(plan || d.split_out || (d.sk_ws && d.sk_ws_bytes >= (int64_t)CTTS_WS_BYTES),
-                 "ctts_gemm: split_k > 1 needs the workspace (ctts_workspace_bytes() bytes, zero-filled once) in sk_ws - partial sums "
-                 "are added in a fixed order through it, the library has no floating-point atomics");
     const long per_split = (long)d.nb0 * d.nb1 * d.M * gemm_partial_ld(d.N);
-    // split_out: the caller keeps the partial matrices and adds them itself later (ctts_partial_sums, many GEMMs per launch) - no reduce launch
-    const long room = plan ? (1L << 60) : (d.split_out ? d.split_out_floats : (long)CTTS_WS_SLAB_FLOATS);
-    const long cap = room / per_split;
-    CTTS_REQUIRE(cap >= 2 && (long)d.M * gemm_partial_ld(d.N) * 4 < 0x7FFF0000L, "ctts_gemm: split-K output [%d, %d] x %d batches does not fit the %s",
-                 d.M, d.N, d.nb0 * d.nb1, d.split_out ? "caller's split_out buffer" : "workspace");
-    if (d.split_k > cap) d.split_k = (int)cap;
+    const long room = unbounded_room ? (1L << 60) : (d.split_out ? d.split_out_floats : (long)CTTS_WS_SLAB_FLOATS);
+    const long cap = per_split > 0 ? room / per_split : 0;
+    r.split_fits = cap >= 2 && (long)d.M * gemm_partial_ld(d.N) * 4 < 0x7FFF0000L;
+    r.info.split_k = d.split_k > cap ? (int)cap : d.split_k;
   }
-  const bool split = d.split_k > 1;
-  const int kround = kind == K_BUF_K2 ? 2 * BK : BK;          // the K granularity of the kernel's split (its `chunk`)
-  if (plan) {
-    if (split && d.nb0 * d.nb1 == 1 && !d.lens && d.K > 0 && !(d.a_kc && d.row_lens)) {
-      const int chunk = ((d.K + d.split_k - 1) / d.split_k + kround - 1) / kround * kround;
-      plan->deferred_ok = 1;
-      plan->count = (d.K + chunk - 1) / chunk;
-      plan->stride = (long)d.M * gemm_partial_ld(d.N);
-    }
-    return 0;
+}
+
+// what ctts_gemm checks before it routes: 0 = go on with `d` (normalised copy), 1 = nothing to do (empty output), < 0 = error
+static int gemm_validate(const ctts_gemm_desc* dp, ctts_gemm_desc& d) {
+  CTTS_REQUIRE(dp != nullptr, "ctts_gemm: null descriptor");
+  d = gemm_normalized(*dp);
+  CTTS_REQUIRE(d.A && d.B && d.C, "ctts_gemm: null operand pointer");
+  CTTS_REQUIRE(d.M >= 0 && d.N >= 0 && d.K >= 0, "ctts_gemm: negative dimension");
+  if (d.M == 0 || d.N == 0) return 1;
+  if (d.conv_T > 0) {
+    CTTS_REQUIRE(d.conv_cin > 0 && (d.conv_cin % 4) == 0, "ctts_gemm: conv view needs cin %% 4 == 0 (got %d)", d.conv_cin);
+    CTTS_REQUIRE(d.conv_on_b ? (!d.a_kc && !d.b_kc) : (d.a_kc != 0), "ctts_gemm: conv view on an unsupported operand layout");
   }
-  const ctts_gemm_desc d_user = d;                 // what the reduce launch accumulates into
+  CTTS_REQUIRE(d.p_drop >= 0.f && d.p_drop < 1.f, "ctts_gemm: p_drop out of range");
+  CTTS_REQUIRE(!d.epi_bwd || (d.split_k <= 1 && !d.bias && !d.R && !d.rowscale && !d.E && (!d.act || d.Z)),
+               "ctts_gemm: epi_bwd excludes bias, residual, rowscale, E and split-K, and needs Z when an activation is given");
+  CTTS_REQUIRE(!d.E || (d.rowsub && d.split_k <= 1 && !d.bias && !d.act && d.p_drop == 0.f && !d.R && !d.rowscale && !d.Z),
+               "ctts_gemm: the E/rowsub epilogue excludes bias, activation, dropout, residual, rowscale and split-K");
+  return 0;
+}
+
+// validate -> route -> a tile-kernel launch with split_k > 1 needs somewhere to put its partial matrices.  Returns like gemm_validate.
+static int gemm_plan(const ctts_gemm_desc* dp, ctts_gemm_desc& d, GemmRoute& r) {
+  const int rc = gemm_validate(dp, d);
+  if (rc != 0) return rc;
+  gemm_route(d, r);
+  if (r.info.kind < CTTS_GEMM_X6TN || d.split_k <= 1) return 0;
+  CTTS_REQUIRE(d.split_out || (d.sk_ws && d.sk_ws_bytes >= (int64_t)CTTS_WS_BYTES),
+               "ctts_gemm: split_k > 1 needs the workspace (ctts_workspace_bytes() bytes, zero-filled once) in sk_ws - partial sums "
+               "are added in a fixed order through it, the library has no floating-point atomics");
+  CTTS_REQUIRE(r.split_fits, "ctts_gemm: split-K output [%d, %d] x %d batches does not fit the %s", d.M, d.N, d.nb0 * d.nb1,
+               d.split_out ? "caller's split_out buffer" : "workspace");
+  return 0;
+}
+
+extern "C" int ctts_gemm(const ctts_gemm_desc* dp, void* stream) {
+  ctts_gemm_desc d;
+  GemmRoute r;
+  int rc = gemm_plan(dp, d, r);
+  if (rc != 0) return rc < 0 ? rc : 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // ---- `t` is the descriptor the tile kernels see (the other families take the caller's)
+  const bool split = r.info.split_k > 1;
+  ctts_gemm_desc t = d;
+  t.tile_group_n = r.tile_group_n;
+  if (r.natural_order) t.tile_map = reinterpret_cast<const int32_t*>(1);
+  if (d.split_k > 1) t.split_k = r.info.split_k;      // (possibly lowered)
+  const ctts_gemm_desc d_user = t;                 // what the reduce launch accumulates into
   if (split) {
     // the tile kernels see the partial matrices as their output: C = P [z][split][M][ldp], plain stores (alpha = 1, no epilogue terms);
     // workgroup (z, split) adds split * M * ldc itself.  Whole tiles of padded rows are "zero-filled" into P_0 and skipped by the reduce.
     const long ldp = gemm_partial_ld(d.N);
-    d.C = d.split_out ? d.split_out : reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(d.sk_ws) + CTTS_WS_SLABS);
-    d.ldc = ldp;
-    d.sC1 = (long)d.split_k * d.M * ldp;
-    d.sC0 = (long)d.nb1 * d.sC1;
-    d.alpha = 1.f; d.bias = nullptr; d.Z = nullptr; d.act = 0; d.p_drop = 0.f; d.R = nullptr; d.rowscale = nullptr;
+    t.C = d.split_out ? d.split_out : reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(d.sk_ws) + CTTS_WS_SLABS);
+    t.ldc = ldp;
+    t.sC1 = (long)t.split_k * d.M * ldp;
+    t.sC0 = (long)d.nb1 * t.sC1;
+    t.alpha = 1.f; t.bias = nullptr; t.Z = nullptr; t.act = 0; t.p_drop = 0.f; t.R = nullptr; t.rowscale = nullptr;
   }
-  int rc;
-  switch (kind) {
-    case K_SCALAR64: rc = dispatch_layout<64, 64, false>(d, st); break;
+  switch (r.info.kind) {
+    case CTTS_GEMM_PLANES: return ctts_gemm_pl_launch(d, r.pl, r.grid, st);
+    case CTTS_GEMM_PLANES_WGRAD: return ctts_gemm_plw_launch(d, r.plw, r.grid, st);
+    case CTTS_GEMM_WEIGHT_STATIONARY: return ctts_gemm_ws_launch(d, r.ws, r.grid, st);
+    case CTTS_GEMM_X6: return x6_launch(d, st);
+    case CTTS_GEMM_STREAM_K: return ctts_gemm_sk_launch(d, r.sk, r.grid, st);
+    case CTTS_GEMM_SCALAR64: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch<64, 64, a(), b(), c(), false>(t, st); }); break;
 #ifndef CTTS_NO_BUF
-    case K_BUF128: rc = dispatch_buf<128, 128>(d, st); break;
-    case K_BUF_K2: rc = dispatch_buf_k2(d, st); break;
-    case K_BUF_NARROW: rc = dispatch_buf_narrow(d, st); break;
-    case K_BUF64: rc = dispatch_buf<64, 64>(d, st); break;
+    case CTTS_GEMM_BUF128: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch_buf<128, 128, a(), b(), c()>(t, st); }); break;
+    case CTTS_GEMM_BUF_K2: rc = dispatch_buf_k2(t, st); break;
+    case CTTS_GEMM_BUF_NARROW: rc = dispatch_buf_narrow(t, st); break;
+    case CTTS_GEMM_BUF64: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch_buf<64, 64, a(), b(), c()>(t, st); }); break;
 #endif
-    case K_VEC128: rc = dispatch_layout<128, 128, true>(d, st); break;
-    case K_X6TN: rc = gemm_x6tn_launch(d, st); break;
-    default: rc = dispatch_layout<64, 64, true>(d, st); break;
+    case CTTS_GEMM_VEC128: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch<128, 128, a(), b(), c(), true>(t, st); }); break;
+    case CTTS_GEMM_X6TN: rc = x6tn_launch(t, st); break;
+    default: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch<64, 64, a(), b(), c(), true>(t, st); }); break;
   }
-  if (rc != 0 || !split || d_user.split_out) return rc;
-  ctts_gemm_desc dr = d_user;
-  dr.split_k = d.split_k;                          // (possibly lowered above)
-  return splitk_reduce(dr, BMs, kround, st);
+  if (rc != 0 || !split || d.split_out) return rc;
+  return splitk_reduce(d_user, r.info.tile_m, r.info.k_granule, st);
 }
 
-extern "C" int ctts_gemm(const ctts_gemm_desc* dp, void* stream) { return gemm_impl(dp, stream, nullptr); }
+extern "C" int ctts_gemm_route(const ctts_gemm_desc* dp, ctts_gemm_route_info* info) {
+  CTTS_REQUIRE(info != nullptr, "ctts_gemm_route: null info");
+  *info = ctts_gemm_route_info{CTTS_GEMM_NONE, 0, 0, 0, 0};
+  ctts_gemm_desc d;
+  GemmRoute r;
+  const int rc = gemm_plan(dp, d, r);
+  if (rc == 0) *info = r.info;
+  return rc < 0 ? rc : 0;
+}
+
+static int route_kind(const ctts_gemm_desc* dp) {          // of an unvalidated descriptor
+  if (!dp) return CTTS_GEMM_NONE;
+  const ctts_gemm_desc d = gemm_normalized(*dp);
+  GemmRoute r;
+  gemm_route(d, r);
+  return r.info.kind;
+}
+extern "C" int ctts_gemm_takes_planes(const ctts_gemm_desc* d) {
+  const int kind = route_kind(d);
+  return kind == CTTS_GEMM_PLANES || kind == CTTS_GEMM_PLANES_WGRAD;
+}
+extern "C" int ctts_gemm_takes_bf16_split(const ctts_gemm_desc* d) {
+  const int kind = route_kind(d);
+  return kind == CTTS_GEMM_X6 || kind == CTTS_GEMM_X6TN;
+}
 
 // Deferred split-K (ctts_gemm_desc.split_out): would ctts_gemm run this descriptor as a split-K launch of the tile kernels whose partial
 // matrices the caller may keep and add later?  Returns 1 and fills *count (partial matrices that will be written: P_0 .. P_count-1) and
-// *stride (floats between them; each is [M, N rounded up to 4] row-major), else 0 (stream-K / weight-stationary take it, split_k <= 1,
-// batched or length-limited launches).  Give ctts_gemm a split_out buffer of at least split_k * stride floats.
+// *stride (floats between them; each is [M, N rounded up to 4] row-major), else 0 (another family takes it, split_k <= 1, batched or
+// length-limited launches).  Give ctts_gemm a split_out buffer of at least split_k * stride floats.
 extern "C" int ctts_gemm_split_plan(const ctts_gemm_desc* dp, int32_t* count, int64_t* stride) {
-  GemmSplitPlan pl = {0, 0, 0};
-  ctts_gemm_desc d = *dp;
+  ctts_gemm_desc d;
+  GemmRoute r;
+  if (gemm_validate(dp, d) != 0 || d.split_k <= 1) return 0;
   d.split_out = nullptr;
-  if (gemm_impl(&d, nullptr, &pl) != 0 || !pl.deferred_ok) return 0;
-  if (count) *count = pl.count;
-  if (stride) *stride = pl.stride;
+  // The plane forward kernel (NT) takes split_k > 1 with split_overwrite as a plain overwrite and writes no partials, yet this query
+  // has always answered for an NT descriptor as if no planes were given (include/ctts.h says so); no caller defers an NT launch.
+  if (d.a_kc) d.A_planes = nullptr;
+  gemm_route(d, r, true);
+  if (r.info.kind < CTTS_GEMM_X6TN || !r.split_fits) return 0;
+  if (d.nb0 * d.nb1 != 1 || d.lens || d.K <= 0 || (d.a_kc && d.row_lens)) return 0;
+  const int chunk = ((d.K + r.info.split_k - 1) / r.info.split_k + r.info.k_granule - 1) / r.info.k_granule * r.info.k_granule;
+  if (count) *count = (d.K + chunk - 1) / chunk;
+  if (stride) *stride = (long)d.M * gemm_partial_ld(d.N);
   return 1;
 }

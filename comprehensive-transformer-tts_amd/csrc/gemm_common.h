@@ -338,17 +338,82 @@ __device__ __forceinline__ void gemm_epilogue_auto(const ctts_gemm_desc& d, floa
 
 }  // namespace
 
-// gemm_sk.hip: persistent stream-K kernel with direct-to-LDS operand loads.  Returns 1 when it took the launch, 0 when the descriptor is
-// not eligible (the caller then uses the tile-per-workgroup kernels), < 0 on error.
-int ctts_gemm_sk_try(const ctts_gemm_desc& d, hipStream_t st);
+// ---- host side: the kernel families outside gemm.hip.  Each has a pure X_plan (eligibility + launch geometry of a descriptor whose nb0 /
+// nb1 are already >= 1: no launch, no stream, no side effects) and an X_launch of what was planned (0, or < 0 on error).  gemm_route in
+// gemm.hip is the only place that puts the families in an order.
+//   gemm_pl.hip: persistent stream-K kernel on pre-split bf16 planes (ctts_gemm_desc.A_planes / B_planes);  gemm_plw.hip: the weight-
+//   gradient (TN) layout on the same plane sets;  gemm_ws.hip: weight-stationary kernel for K = 256 (the weight slice of a workgroup
+//   lives in registers, A tiles stream through LDS);  gemm_sk.hip: persistent stream-K kernel with direct-to-LDS operand loads.
+// The kernels' argument structs stay in the unnamed namespace (the kernels keep their names); C linkage is what lets a function with
+// such a parameter be called from another translation unit.
+// CAUTION: every translation unit therefore has its OWN PlArgs / PlwArgs / SkArgs / WsArgs, and a call across units works only because
+// the layouts are identical: keep these four structs plain data (no constructors, no virtuals), and define them here and nowhere else.
+namespace {
+struct PlArgs {
+  int tiles_m, tiles_n;      // static tile grid (128 x 256 tiles); tiles_m counts ALL m-tiles (the active count comes from row_lens)
+  int nkb;                   // K-blocks per tile
+  int gw;                    // n-tiles per schedule group
+  int whole_tiles;           // 1: never split a tile
+  int ntap;                  // conv view: taps (K / cin); K is walked (channel block, tap)
+  int nutt, tpu;             // ragged rows: utterances and 128-row tiles per utterance (nutt = 0: dense)
+  int debug;                 // CTTS_PL_DEBUG (tools): 1 = no DMA after the prologue, 4 = no epilogue, 8 = no MFMA, 32 = no rotated order in the upper wave group, 16 = record shader cycles / wall ticks of workgroup 8 in the workspace header
+  unsigned* ws;
+};
 
-// gemm_ws.hip: weight-stationary kernel for K = 256 (the weight slice of a workgroup lives in registers, A tiles stream through LDS).
-// Same return convention.
-int ctts_gemm_ws_try(const ctts_gemm_desc& d, hipStream_t st);
+struct PlwArgs {
+  int tiles_m, tiles_n;      // 128 x 256 tiles of the [M, N] output
+  int nkb;                   // 32-row K-blocks of the reduction (dense; ragged: computed in the kernel from row_lens)
+  int nutt, kbu;             // ragged rows: utterances and K-blocks per utterance (row_T / 32); nutt = 0: dense
+  int fold_tt, fold_tiles;   // conv, conv_T % 32 == 0: the first `fold_tiles` n-tiles are FOLDED - 256 columns = fold_tt taps x 256 / fold_tt channels,
+                             // served by ONE B image of 32 + fold_tt - 1 rows (fold_tt = 1: no folding); the remaining taps: one tap per tile
+  int accumulate;            // 1: C += alpha * acc
+  int debug;                 // CTTS_PL_DEBUG bits of gemm_pl.hip (tools builds)
+  unsigned* ws;
+};
 
-// gemm_pl.hip: persistent stream-K kernel on pre-split bf16 planes (ctts_gemm_desc.A_planes / B_planes).  Same return convention.
-int ctts_gemm_pl_try(const ctts_gemm_desc& d, hipStream_t st);
+struct SkArgs {
+  int tiles_m, tiles_n;      // static tile grid (BM x BN tiles)
+  int nkb;                   // K-blocks per tile when no K-block schedule is given
+  int gw;                    // n-tiles per schedule group
+  int whole_tiles;           // 1: never split a tile
+  int accumulate;            // 1: C += alpha * acc (weight gradients), no other epilogue
+  int conv_chan_major;       // conv view on A: walk K as (channel block, tap) instead of (tap, channel block) - see k0_of
+  int debug;                 // CTTS_SK_DEBUG (tools only): 1 = no DMA after the first block, 2 = every workgroup loads tile (0,0), 4 = no epilogue, 16 = record shader cycles / wall ticks of workgroup 8 in the workspace header
+  unsigned* ws;              // workspace: SK_FLAG_WORDS words, then one slab per workgroup
+};
 
-// gemm_plw.hip: the weight-gradient (TN) layout on the same plane sets.  _try: same return convention; _takes: 1 / 0 without launching.
-int ctts_gemm_plw_try(const ctts_gemm_desc& d, hipStream_t st);
-int ctts_gemm_plw_takes(const ctts_gemm_desc& d);
+struct WsArgs {
+  int tiles_m;         // ceil(M / 64)
+  int n_blocks;        // ceil(N / 128)
+  int wg_per_block;    // workgroups that share one 128-column block (grid = n_blocks * wg_per_block)
+  int xcd_aligned;     // 1: the n-blocks of one m-tile sequence sit on one XCD (wg_per_block % 8 == 0)
+  int debug;           // CTTS_WS_DEBUG: 1 = per-workgroup phase clocks into the tail of sk_ws, 2 = no epilogue, 4 = no in-loop DMA, 8 = no MFMA
+};
+}  // namespace
+struct GemmGrid { int tile_m, tile_n, grid, stages; };      // workgroup tile, workgroups, LDS stages (stream-K only)
+extern "C" {
+bool ctts_gemm_pl_plan(const ctts_gemm_desc& d, PlArgs& p, GemmGrid& g);
+int ctts_gemm_pl_launch(const ctts_gemm_desc& d, const PlArgs& p, const GemmGrid& g, hipStream_t st);
+bool ctts_gemm_plw_plan(const ctts_gemm_desc& d, PlwArgs& p, GemmGrid& g);
+int ctts_gemm_plw_launch(const ctts_gemm_desc& d, const PlwArgs& p, const GemmGrid& g, hipStream_t st);
+bool ctts_gemm_ws_plan(const ctts_gemm_desc& d, WsArgs& p, GemmGrid& g);
+int ctts_gemm_ws_launch(const ctts_gemm_desc& d, const WsArgs& p, const GemmGrid& g, hipStream_t st);
+bool ctts_gemm_sk_plan(const ctts_gemm_desc& d, SkArgs& p, GemmGrid& g);
+int ctts_gemm_sk_launch(const ctts_gemm_desc& d, const SkArgs& p, const GemmGrid& g, hipStream_t st);
+}
+
+// what every entry point does to its copy of the caller's descriptor first
+static inline ctts_gemm_desc gemm_normalized(const ctts_gemm_desc& in) {
+  ctts_gemm_desc d = in;
+  if (d.nb0 < 1) d.nb0 = 1;
+  if (d.nb1 < 1) d.nb1 = 1;
+  return d;
+}
+
+// a family's plan asked on its own (ctts_gemm_takes_persistent / _weight_stationary)
+template <class Args>
+int gemm_takes(const ctts_gemm_desc* d, bool (*plan)(const ctts_gemm_desc&, Args&, GemmGrid&)) {
+  Args p;
+  GemmGrid g;
+  return (d && plan(gemm_normalized(*d), p, g)) ? 1 : 0;
+}

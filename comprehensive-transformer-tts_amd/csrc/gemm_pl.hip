@@ -24,24 +24,13 @@
 //   * ragged (b, t) rows: the schedule of the ACTIVE 128-row tiles is built by every workgroup itself from row_lens (prefix sums in LDS;
 //     row_T % 128 == 0), wholly padded tiles are zero-filled, and - the zero rule has 64-row granularity in the other kernels - the waves
 //     that own a wholly padded upper half of an active tile write zeros instead of their epilogue.
-// Eligibility: pl_try below.  Everything else stays on gemm.hip / gemm_sk.hip / gemm_ws.hip.
+// Eligibility: ctts_gemm_pl_plan below.  Everything else stays on gemm.hip / gemm_sk.hip / gemm_ws.hip.
 #include "gemm_pl_common.h"
 #include "planes_common.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
-
-struct PlArgs {
-  int tiles_m, tiles_n;      // static tile grid (128 x 256 tiles); tiles_m counts ALL m-tiles (the active count comes from row_lens)
-  int nkb;                   // K-blocks per tile
-  int gw;                    // n-tiles per schedule group
-  int whole_tiles;           // 1: never split a tile
-  int ntap;                  // conv view: taps (K / cin); K is walked (channel block, tap)
-  int nutt, tpu;             // ragged rows: utterances and 128-row tiles per utterance (nutt = 0: dense)
-  int debug;                 // CTTS_PL_DEBUG (tools): 1 = no DMA after the prologue, 4 = no epilogue, 8 = no MFMA, 32 = no rotated order in the upper wave group, 16 = record shader cycles / wall ticks of workgroup 8 in the workspace header
-  unsigned* ws;
-};
 
 // The epilogues this kernel carries (pl_epilogue_ok is the host-side twin: descriptors with any other combination are not taken).  Only
 // lean variants: the generic epilogue and the full dispatch of gemm_epilogue_auto (14 variants) cost this kernel 12 - 27 spilled VGPRs
@@ -475,11 +464,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
   else run(std::false_type{});
 }
 
-int pl_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 // ---------------------------------------------------------------- exact three-way bf16 split of fp32 matrices (many per launch)
 constexpr int SPL_BATCH = 32;          // all weight sets of an fs2 step (26 matrices) in ONE launch
 struct SplitBatch {
@@ -539,38 +523,37 @@ extern "C" int ctts_split_planes(const ctts_split_task* tasks, int ntasks, void*
   return 0;
 }
 
-// launch == false: only answer whether the plane kernel WOULD take this descriptor (ctts_gemm_takes_planes)
-static int pl_try(const ctts_gemm_desc& d, hipStream_t st, bool launch) {
-  static const int enabled = pl_env("CTTS_PL", 1);
-  static const int min_units = pl_env("CTTS_PL_MIN_UNITS", 4096);     // (tile, K-block) units; below this the launch is latency bound either way
-  static const int split_from = pl_env("CTTS_PL_SPLIT_NKB", 24);
+// eligibility + grid of the plane kernel
+extern "C" bool ctts_gemm_pl_plan(const ctts_gemm_desc& d, PlArgs& p, GemmGrid& g) {
+  static const int enabled = ctts_env_int("CTTS_PL", 1);
+  static const int min_units = ctts_env_int("CTTS_PL_MIN_UNITS", 4096);     // (tile, K-block) units; below this the launch is latency bound either way
+  static const int split_from = ctts_env_int("CTTS_PL_SPLIT_NKB", 24);
   // pieces a tile may be cut into when the tile count alone cannot fill the chip (2,048-row launches: 64 tiles).  2 until the slab
   // hand-off stopped costing ~16 us per slab (see the owner's loop); with ~4 us per slab: encoder FFN conv forward 93 -> 64 us at 4,
   // its data gradient (16 tiles x 288 K-blocks) 156 -> 92 us at 8
-  static const int max_split = pl_env("CTTS_PL_MAX_SPLIT", 8);
-  static const int wg_units = pl_env("CTTS_PL_WG_UNITS", 16);
-  static const int force_w = pl_env("CTTS_PL_W", 0);
-  static const int debug = pl_env("CTTS_PL_DEBUG", 0);
-  if (!enabled || d.bf16_split < 1 || !d.A_planes || !d.B_planes) return 0;
-  if (!d.sk_ws || d.sk_ws_bytes < (int64_t)CTTS_WS_BYTES) return 0;
-  if (!d.a_kc || !d.b_kc || d.nb0 * d.nb1 != 1 || d.lens || d.E) return 0;
-  if (d.split_k > 1 && !d.split_overwrite) return 0;                 // "C += alpha A B" is not built here
-  if (d.K % 32 != 0 || d.K < 64 || d.N % 128 != 0 || d.N < 256 || d.M < 128) return 0;
+  static const int max_split = ctts_env_int("CTTS_PL_MAX_SPLIT", 8);
+  static const int wg_units = ctts_env_int("CTTS_PL_WG_UNITS", 16);
+  static const int force_w = ctts_env_int("CTTS_PL_W", 0);
+  static const int debug = ctts_env_int("CTTS_PL_DEBUG", 0);
+  if (!enabled || d.bf16_split < 1 || !d.A_planes || !d.B_planes) return false;
+  if (!d.sk_ws || d.sk_ws_bytes < (int64_t)CTTS_WS_BYTES) return false;
+  if (!d.a_kc || !d.b_kc || d.nb0 * d.nb1 != 1 || d.lens || d.E) return false;
+  if (d.split_k > 1 && !d.split_overwrite) return false;                 // "C += alpha A B" is not built here
+  if (d.K % 32 != 0 || d.K < 64 || d.N % 128 != 0 || d.N < 256 || d.M < 128) return false;
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!al16(d.A_planes) || !al16(d.B_planes) || ((d.lda | d.ldb) & 31)) return 0;
+  if (!al16(d.A_planes) || !al16(d.B_planes) || ((d.lda | d.ldb) & 31)) return false;
   const bool conv = d.conv_T > 0;
-  if (conv && (d.conv_on_b || d.conv_cin % 32 != 0 || d.K % d.conv_cin != 0 || d.conv_T < 16)) return 0;
+  if (conv && (d.conv_on_b || d.conv_cin % 32 != 0 || d.K % d.conv_cin != 0 || d.conv_T < 16)) return false;
   // 32-bit buffer offsets over the three planes (plus a tile of rows beyond M and the conv shift)
   const long a_ext = (long)(d.M + 256) * d.lda * 3 + 3L * d.K;
   const long b_ext = (long)(d.N + 256) * d.ldb * 3 + 3L * d.K;
-  if (a_ext * 2 >= 0x7FFF0000L || b_ext * 2 >= 0x7FFF0000L) return 0;
-  if (pl_epilogue_kind(d) < 0) return 0;          // only the lean epilogues the kernel carries
-  PlArgs p;
+  if (a_ext * 2 >= 0x7FFF0000L || b_ext * 2 >= 0x7FFF0000L) return false;
+  if (pl_epilogue_kind(d) < 0) return false;          // only the lean epilogues the kernel carries
   p.nutt = p.tpu = 0;
   p.tiles_m = (d.M + PL_BM - 1) / PL_BM;
   long act_tiles_m = p.tiles_m;
   if (d.row_lens) {
-    if (d.row_T <= 0 || d.row_T % PL_BM != 0 || d.M % d.row_T != 0 || d.M / d.row_T > PL_MAX_UTT) return 0;
+    if (d.row_T <= 0 || d.row_T % PL_BM != 0 || d.M % d.row_T != 0 || d.M / d.row_T > PL_MAX_UTT) return false;
     p.nutt = d.M / d.row_T;
     p.tpu = d.row_T / PL_BM;
   }
@@ -586,7 +569,7 @@ static int pl_try(const ctts_gemm_desc& d, hipStream_t st, bool launch) {
   const long tiles = act_tiles_m * p.tiles_n;
   const long units = tiles * p.nkb;
   const bool forced = d.bf16_split == 2 || d.bf16_split == 4;        // no size thresholds (parity tests of small launches)
-  if (!forced && units < min_units) return 0;
+  if (!forced && units < min_units) return false;
   const int cuts = p.whole_tiles ? 1 : ((p.nkb >= 256 && max_split < 4) ? 4 : max_split);
   long W = force_w > 0 ? force_w : 32;
   const long Wu = units / (8L * wg_units);
@@ -596,29 +579,16 @@ static int pl_try(const ctts_gemm_desc& d, hipStream_t st, bool launch) {
   const long Wt = (d.row_lens && p.tpu >= 4) ? (tiles * cuts * 3 / 4) / 8 : (tiles * cuts) / 8;
   if (W > Wt) W = Wt;
   if (W < 1) {
-    if (!forced) return 0;
+    if (!forced) return false;
     W = 1;
   }
   const int grid = (int)W * 8;
-  if (grid > PL_MAX_WG || (long)grid * PL_SLAB > PL_SLAB_FLOATS_MAX) return 0;
-  if (!launch) return 1;
-  if (d.bf16_split >= 3) {
-    if (conv) hipLaunchKernelGGL((gemm_pl_kernel<true, 1>), dim3(grid), dim3(512), 0, st, d, p);
-    else hipLaunchKernelGGL((gemm_pl_kernel<false, 1>), dim3(grid), dim3(512), 0, st, d, p);
-  } else {
-    if (conv) hipLaunchKernelGGL((gemm_pl_kernel<true, 6>), dim3(grid), dim3(512), 0, st, d, p);
-    else hipLaunchKernelGGL((gemm_pl_kernel<false, 6>), dim3(grid), dim3(512), 0, st, d, p);
-  }
-  CTTS_CHECK_LAUNCH("ctts_gemm(planes)");
-  return 1;
+  if (grid > PL_MAX_WG || (long)grid * PL_SLAB > PL_SLAB_FLOATS_MAX) return false;
+  g.tile_m = PL_BM; g.tile_n = PL_BN;
+  g.grid = grid;
+  return true;
 }
 
-int ctts_gemm_pl_try(const ctts_gemm_desc& d, hipStream_t st) { return pl_try(d, st, true); }
-
-extern "C" int ctts_gemm_takes_planes(const ctts_gemm_desc* d) {
-  if (!d) return 0;
-  ctts_gemm_desc c = *d;
-  if (c.nb0 < 1) c.nb0 = 1;
-  if (c.nb1 < 1) c.nb1 = 1;
-  return (pl_try(c, nullptr, false) > 0 || ctts_gemm_plw_takes(c)) ? 1 : 0;
+extern "C" int ctts_gemm_pl_launch(const ctts_gemm_desc& d, const PlArgs& p, const GemmGrid& g, hipStream_t st) {
+  return pl_launch(gemm_pl_kernel<true, 1>, gemm_pl_kernel<false, 1>, gemm_pl_kernel<true, 6>, gemm_pl_kernel<false, 6>, d, p, g.grid, st, "ctts_gemm(planes)");
 }

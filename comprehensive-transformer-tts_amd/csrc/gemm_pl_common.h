@@ -55,4 +55,13 @@ __device__ __forceinline__ floatx16 pl_mma(const pl_u32x4 a, const pl_u32x4 b, c
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(pl_bf16x8, a), __builtin_bit_cast(pl_bf16x8, b), c, 0, 0, 0);
 }
 
+// host side: a plane kernel has four instantiations - conv view on / off x one MFMA term (the "amp" arithmetic, bf16_split 3 / 4) or six
+template <class Kern, class Args>
+int pl_launch(Kern conv_1, Kern dense_1, Kern conv_6, Kern dense_6, const ctts_gemm_desc& d, const Args& p, int grid, hipStream_t st, const char* what) {
+  const Kern k = d.bf16_split >= 3 ? (d.conv_T > 0 ? conv_1 : dense_1) : (d.conv_T > 0 ? conv_6 : dense_6);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(512), 0, st, d, p);
+  CTTS_CHECK_LAUNCH(what);
+  return 0;
+}
+
 }  // namespace

@@ -24,7 +24,7 @@
 //     instruction order of the upper wave group, the even unit partition and the fixed-order slab hand-off: as in gemm_pl.hip;
 //   * epilogue: C = alpha * acc or C += alpha * acc (what split_k > 1 without split_overwrite means in ctts_gemm) by the tile's owner -
 //     the weight gradient is added to param.grad in place, in a fixed order, without partial matrices and without a reduce launch.
-// Eligibility: plw_try below; everything else stays on gemm_x6tn_kernel / the fp32 kernels.
+// Eligibility: ctts_gemm_plw_plan below; everything else stays on gemm_x6tn_kernel / the fp32 kernels.
 #include "gemm_pl_common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -37,17 +37,6 @@ typedef __attribute__((address_space(3))) plw_s16x4 plw_lds_s16x4;
 constexpr int PLW_A_PLANE = 32 * PL_BM * 2;          // one piece of the A image: [32 k][128 m] bf16 = 8 KB
 constexpr int PLW_B_PLANE = 32 * PL_BN * 2;          // [32 k][256 n] bf16 = 16 KB
 static_assert(3 * (PLW_A_PLANE + PLW_B_PLANE) == PL_STAGE, "same stage size as gemm_pl_kernel");
-
-struct PlwArgs {
-  int tiles_m, tiles_n;      // 128 x 256 tiles of the [M, N] output
-  int nkb;                   // 32-row K-blocks of the reduction (dense; ragged: computed in the kernel from row_lens)
-  int nutt, kbu;             // ragged rows: utterances and K-blocks per utterance (row_T / 32); nutt = 0: dense
-  int fold_tt, fold_tiles;   // conv, conv_T % 32 == 0: the first `fold_tiles` n-tiles are FOLDED - 256 columns = fold_tt taps x 256 / fold_tt channels,
-                             // served by ONE B image of 32 + fold_tt - 1 rows (fold_tt = 1: no folding); the remaining taps: one tap per tile
-  int accumulate;            // 1: C += alpha * acc
-  int debug;                 // CTTS_PL_DEBUG bits of gemm_pl.hip (tools builds)
-  unsigned* ws;
-};
 
 // 24 x (one MFMA, one LDS read) in program order for the scheduling region that ends here (masks: 0x008 MFMA, 0x100 DS read)
 #define PLW_SGB2() __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0)
@@ -478,46 +467,40 @@ __global__ __launch_bounds__(512, 2) void gemm_plw_kernel(const ctts_gemm_desc d
   else run(std::false_type{});
 }
 
-int plw_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 }  // namespace
 
-// launch == false: only answer whether this kernel WOULD take the descriptor
-static int plw_try(const ctts_gemm_desc& d, hipStream_t st, bool launch) {
-  static const int enabled = plw_env("CTTS_PLW", 1);
-  static const int min_units = plw_env("CTTS_PLW_MIN_UNITS", 4096);
-  static const int wg_units = plw_env("CTTS_PLW_WG_UNITS", 16);
+// eligibility + grid of the weight-gradient plane kernel
+extern "C" bool ctts_gemm_plw_plan(const ctts_gemm_desc& d, PlwArgs& p, GemmGrid& g) {
+  static const int enabled = ctts_env_int("CTTS_PLW", 1);
+  static const int min_units = ctts_env_int("CTTS_PLW_MIN_UNITS", 4096);
+  static const int wg_units = ctts_env_int("CTTS_PLW_WG_UNITS", 16);
   // few output tiles = every tile cut into many pieces, whose slabs the owner adds one after the other (25 pieces per tile: 198 us for the
   // [256 x 1280] gradient that the split-K kernel with its parallel reduce launch finishes in 92): such launches stay where they are
-  static const int min_tiles = plw_env("CTTS_PLW_MIN_TILES", 32);
-  static const int force_w = plw_env("CTTS_PLW_W", 0);
-  static const int debug = plw_env("CTTS_PL_DEBUG", 0);
-  if (!enabled || d.bf16_split < 1 || !d.A_planes || !d.B_planes) return 0;
-  if (!d.sk_ws || d.sk_ws_bytes < (int64_t)CTTS_WS_BYTES) return 0;
-  if (d.a_kc || d.b_kc || d.nb0 * d.nb1 != 1 || d.lens || d.E || d.epi_bwd || d.split_out) return 0;
-  if (d.bias || d.act || d.Z || d.R || d.rowscale || d.p_drop > 0.f) return 0;          // a weight gradient has no epilogue terms
-  if (d.M % PL_BM != 0 || d.N % PL_BN != 0 || d.K < 64) return 0;
+  static const int min_tiles = ctts_env_int("CTTS_PLW_MIN_TILES", 32);
+  static const int force_w = ctts_env_int("CTTS_PLW_W", 0);
+  static const int debug = ctts_env_int("CTTS_PL_DEBUG", 0);
+  if (!enabled || d.bf16_split < 1 || !d.A_planes || !d.B_planes) return false;
+  if (!d.sk_ws || d.sk_ws_bytes < (int64_t)CTTS_WS_BYTES) return false;
+  if (d.a_kc || d.b_kc || d.nb0 * d.nb1 != 1 || d.lens || d.E || d.epi_bwd || d.split_out) return false;
+  if (d.bias || d.act || d.Z || d.R || d.rowscale || d.p_drop > 0.f) return false;          // a weight gradient has no epilogue terms
+  if (d.M % PL_BM != 0 || d.N % PL_BN != 0 || d.K < 64) return false;
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!al16(d.A_planes) || !al16(d.B_planes) || ((d.lda | d.ldb) & 31) || d.lda < d.M) return 0;
+  if (!al16(d.A_planes) || !al16(d.B_planes) || ((d.lda | d.ldb) & 31) || d.lda < d.M) return false;
   const bool conv = d.conv_T > 0;
   if (conv) {
-    if (!d.conv_on_b || d.conv_cin % PL_BN != 0 || d.N % d.conv_cin != 0 || d.ldb < d.conv_cin || d.conv_T < 32) return 0;
-    if (d.conv_pad < 0 || d.conv_pad >= d.conv_T || d.N / d.conv_cin - 1 - d.conv_pad >= d.conv_T) return 0;
+    if (!d.conv_on_b || d.conv_cin % PL_BN != 0 || d.N % d.conv_cin != 0 || d.ldb < d.conv_cin || d.conv_T < 32) return false;
+    if (d.conv_pad < 0 || d.conv_pad >= d.conv_T || d.N / d.conv_cin - 1 - d.conv_pad >= d.conv_T) return false;
   } else if (d.ldb < d.N) {
-    return 0;
+    return false;
   }
   // 32-bit buffer offsets over the plane sets (plus a K-block beyond the last row and the conv shift)
   const long a_ext = (long)(d.K + 64) * d.lda * 6, b_ext = (long)(d.K + 64 + (conv ? d.N / d.conv_cin : 0)) * d.ldb * 6;
-  if (a_ext >= 0x7FFF0000L || b_ext >= 0x7FFF0000L) return 0;
-  PlwArgs p;
+  if (a_ext >= 0x7FFF0000L || b_ext >= 0x7FFF0000L) return false;
   p.nutt = p.kbu = 0;
   p.nkb = (d.K + 31) / 32;
   if (d.row_lens) {
-    if (d.row_T <= 0 || d.row_T % 32 != 0 || d.K % d.row_T != 0 || d.K / d.row_T > PL_MAX_UTT) return 0;
-    if (conv && d.row_T != d.conv_T) return 0;
+    if (d.row_T <= 0 || d.row_T % 32 != 0 || d.K % d.row_T != 0 || d.K / d.row_T > PL_MAX_UTT) return false;
+    if (conv && d.row_T != d.conv_T) return false;
     p.nutt = d.K / d.row_T;
     p.kbu = d.row_T / 32;
   }
@@ -525,7 +508,7 @@ static int plw_try(const ctts_gemm_desc& d, hipStream_t st, bool launch) {
   p.tiles_n = d.N / PL_BN;
   p.accumulate = (d.split_k > 1 && !d.split_overwrite) ? 1 : 0;
   // tap folding (tile_kind in the kernel): conv view, every 32-row K-block inside one utterance, at least two taps
-  static const int fold = plw_env("CTTS_PLW_FOLD", 1);
+  static const int fold = ctts_env_int("CTTS_PLW_FOLD", 1);
   p.fold_tt = 1; p.fold_tiles = 0;
   if (fold && conv && d.conv_T % 32 == 0 && d.K % d.conv_T == 0) {       // (whole utterances: the extra rows of a folded image are tested against [0, T) only)
     const int ntap = d.N / d.conv_cin;
@@ -537,24 +520,18 @@ static int plw_try(const ctts_gemm_desc& d, hipStream_t st, bool launch) {
   const long tiles = (long)p.tiles_m * p.tiles_n;
   const long units = tiles * p.nkb;
   const bool forced = d.bf16_split == 2 || d.bf16_split == 4;        // no size thresholds (parity tests of small launches)
-  if (!forced && (units < min_units || tiles < min_tiles)) return 0;
+  if (!forced && (units < min_units || tiles < min_tiles)) return false;
   long W = force_w > 0 ? force_w : 32;
   const long Wu = units / (8L * wg_units);
   if (W > Wu) W = Wu;
   if (W < 1) W = 1;
   const int grid = (int)W * 8;
-  if (grid > PL_MAX_WG || (long)grid * PL_SLAB > PL_SLAB_FLOATS_MAX) return 0;
-  if (!launch) return 1;
-  if (d.bf16_split >= 3) {
-    if (conv) hipLaunchKernelGGL((gemm_plw_kernel<true, 1>), dim3(grid), dim3(512), 0, st, d, p);
-    else hipLaunchKernelGGL((gemm_plw_kernel<false, 1>), dim3(grid), dim3(512), 0, st, d, p);
-  } else {
-    if (conv) hipLaunchKernelGGL((gemm_plw_kernel<true, 6>), dim3(grid), dim3(512), 0, st, d, p);
-    else hipLaunchKernelGGL((gemm_plw_kernel<false, 6>), dim3(grid), dim3(512), 0, st, d, p);
-  }
-  CTTS_CHECK_LAUNCH("ctts_gemm(planes, weight gradient)");
-  return 1;
+  if (grid > PL_MAX_WG || (long)grid * PL_SLAB > PL_SLAB_FLOATS_MAX) return false;
+  g.tile_m = PL_BM; g.tile_n = PL_BN;
+  g.grid = grid;
+  return true;
 }
 
-int ctts_gemm_plw_try(const ctts_gemm_desc& d, hipStream_t st) { return plw_try(d, st, true); }
-int ctts_gemm_plw_takes(const ctts_gemm_desc& d) { return plw_try(d, nullptr, false) > 0 ? 1 : 0; }
+extern "C" int ctts_gemm_plw_launch(const ctts_gemm_desc& d, const PlwArgs& p, const GemmGrid& g, hipStream_t st) {
+  return pl_launch(gemm_plw_kernel<true, 1>, gemm_plw_kernel<false, 1>, gemm_plw_kernel<true, 6>, gemm_plw_kernel<false, 6>, d, p, g.grid, st, "ctts_gemm(planes, weight gradient)");
+}

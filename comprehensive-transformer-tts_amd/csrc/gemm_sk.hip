@@ -13,7 +13,7 @@
 //     free without padding.  A row-contiguous operand tile (32 k-rows x 64 floats) needs no swizzle (ds_read_b32 along the row).
 //   * masked chunks (rows / columns beyond the operand, conv time-boundary taps, K tail rows) use the buffer descriptor's range check:
 //     offset 0x80000000 makes the DMA write zeros.
-// Eligibility (ctts_gemm_sk_try): unbatched, no per-batch length limits, 16-byte aligned operands, K % 32 == 0 for K-contiguous
+// Eligibility (ctts_gemm_sk_plan): unbatched, no per-batch length limits, 16-byte aligned operands, K % 32 == 0 for K-contiguous
 // operands, conv views with cin % 32 == 0.  Everything else stays on gemm.hip.
 #include "ctts_common.h"
 #include "gemm_common.h"
@@ -31,17 +31,6 @@ constexpr unsigned SK_OOB = 0x80000000u;
 constexpr int SK_FLAG_WORDS = 4096;            // header of the workspace: flags[0..2047], error word at [2048]
 constexpr int SK_SLAB_FLOATS_MAX = 2048 * 4096; // slab area: grid x (BM x BN) floats never exceeds this (host check)
 constexpr int SK_MAX_WG = 2048;
-
-struct SkArgs {
-  int tiles_m, tiles_n;      // static tile grid (BM x BN tiles)
-  int nkb;                   // K-blocks per tile when no K-block schedule is given
-  int gw;                    // n-tiles per schedule group
-  int whole_tiles;           // 1: never split a tile
-  int accumulate;            // 1: C += alpha * acc (weight gradients), no other epilogue
-  int conv_chan_major;       // conv view on A: walk K as (channel block, tap) instead of (tap, channel block) - see k0_of
-  int debug;                 // CTTS_SK_DEBUG (tools only): 1 = no DMA after the first block, 2 = every workgroup loads tile (0,0), 4 = no epilogue, 16 = record shader cycles / wall ticks of workgroup 8 in the workspace header
-  unsigned* ws;              // workspace: SK_FLAG_WORDS words, then one slab per workgroup
-};
 
 typedef int sk_i32x4 __attribute__((ext_vector_type(4)));
 
@@ -452,18 +441,13 @@ int sk_launch(const ctts_gemm_desc& d, const SkArgs& p, int grid, int stages, in
   else if (mt == 1 && nt == 2) SK_GO(2, 1, 2);
   else if (mt == 2 && nt == 2) SK_GO(2, 2, 2);
   else if (mt == 1 && nt == 4) {
-    if constexpr (A_KC && B_KC) SK_GO(2, 1, 4);       // the wide tile is only routed for NT launches (sk_try)
+    if constexpr (A_KC && B_KC) SK_GO(2, 1, 4);       // the wide tile is only routed for NT launches (ctts_gemm_sk_plan)
     else { ctts_set_error("ctts_gemm(stream-K): the 64x256 tile is instantiated for the NT layout only"); return -1; }
   }
   else { ctts_set_error("ctts_gemm(stream-K): tile %dx%d not instantiated", mt, nt); return -1; }
 #undef SK_GO
   CTTS_CHECK_LAUNCH("ctts_gemm(stream-K)");
-  return 1;
-}
-
-int sk_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
+  return 0;
 }
 
 }  // namespace
@@ -498,39 +482,38 @@ extern "C" const uint32_t* ctts_workspace_error_word(const void* ws) {
 static_assert((size_t)SK_FLAG_WORDS * 4 <= CTTS_WS_GEMM_TICKETS, "stream-K flag words overlap the split-K tickets");
 static_assert((size_t)SK_SLAB_FLOATS_MAX <= CTTS_WS_SLAB_FLOATS, "stream-K slabs exceed the workspace slab area");
 
-// launch == false: only answer whether the persistent kernel WOULD take this descriptor (ctts_gemm_takes_persistent)
-static int sk_try(const ctts_gemm_desc& din, hipStream_t st, bool launch) {
-  static const int enabled = sk_env("CTTS_SK", 1);
-  static const int stages = sk_env("CTTS_SK_STAGES", 2) == 3 ? 3 : 2; // LDS stages
-  static const int force_w = sk_env("CTTS_SK_W", 0);                  // workgroups per XCD (0 = by LDS footprint)
-  static const int min_units = sk_env("CTTS_SK_MIN_UNITS", 4096);     // below this the launch is latency bound either way
-  static const int split_from = sk_env("CTTS_SK_SPLIT_NKB", 24);      // tiles are cut only when K has at least this many blocks
-  static const int force_gw = sk_env("CTTS_SK_GW", 0);
-  static const int min_nkb = sk_env("CTTS_SK_MIN_NKB", 64);           // K >= 2048: with shorter reductions the tile-per-workgroup kernels win
-  static const int tile_cfg = sk_env("CTTS_SK_TILE", 22);             // 11: 64x64, 12: 64x128, 22: 128x128 workgroup tiles
-  static const int max_split = sk_env("CTTS_SK_MAX_SPLIT", 2);        // tiles * max_split >= grid: a tile is cut in two or three, never more (the owner gathers serially)
-  static const int debug = sk_env("CTTS_SK_DEBUG", 0);
-  static const int wg_units = sk_env("CTTS_SK_WG_UNITS", 16);         // a workgroup gets at least this many (tile, K-block) units
-  const ctts_gemm_desc& d = din;
-  if (!enabled || !d.sk_ws || d.sk_ws_bytes < (int64_t)ctts_gemm_workspace_bytes()) return 0;
-  if (d.nb0 * d.nb1 != 1 || (d.lens && (d.lim_m || d.lim_n || d.lim_k)) || d.E) return 0;
-  if (!d.a_kc && d.b_kc) return 0;
+// eligibility, tile and grid of the persistent kernel
+extern "C" bool ctts_gemm_sk_plan(const ctts_gemm_desc& d, SkArgs& p, GemmGrid& g) {
+  static const int enabled = ctts_env_int("CTTS_SK", 1);
+  static const int stages = ctts_env_int("CTTS_SK_STAGES", 2) == 3 ? 3 : 2; // LDS stages
+  static const int force_w = ctts_env_int("CTTS_SK_W", 0);                  // workgroups per XCD (0 = by LDS footprint)
+  static const int min_units = ctts_env_int("CTTS_SK_MIN_UNITS", 4096);     // below this the launch is latency bound either way
+  static const int split_from = ctts_env_int("CTTS_SK_SPLIT_NKB", 24);      // tiles are cut only when K has at least this many blocks
+  static const int force_gw = ctts_env_int("CTTS_SK_GW", 0);
+  static const int min_nkb = ctts_env_int("CTTS_SK_MIN_NKB", 64);           // K >= 2048: with shorter reductions the tile-per-workgroup kernels win
+  static const int tile_cfg = ctts_env_int("CTTS_SK_TILE", 22);             // 11: 64x64, 12: 64x128, 22: 128x128 workgroup tiles
+  static const int max_split = ctts_env_int("CTTS_SK_MAX_SPLIT", 2);        // tiles * max_split >= grid: a tile is cut in two or three, never more (the owner gathers serially)
+  static const int debug = ctts_env_int("CTTS_SK_DEBUG", 0);
+  static const int wg_units = ctts_env_int("CTTS_SK_WG_UNITS", 16);         // a workgroup gets at least this many (tile, K-block) units
+  if (!enabled || !d.sk_ws || d.sk_ws_bytes < (int64_t)ctts_gemm_workspace_bytes()) return false;
+  if (d.nb0 * d.nb1 != 1 || (d.lens && (d.lim_m || d.lim_n || d.lim_k)) || d.E) return false;
+  if (!d.a_kc && d.b_kc) return false;
   const bool tn = !d.a_kc && !d.b_kc;
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!al16(d.A) || !al16(d.B) || ((d.lda | d.ldb) & 3)) return 0;
-  if (d.a_kc ? (d.K % 32 != 0) : (d.M % 4 != 0)) return 0;
-  if (d.b_kc ? (d.K % 32 != 0) : (d.N % 4 != 0)) return 0;
+  if (!al16(d.A) || !al16(d.B) || ((d.lda | d.ldb) & 3)) return false;
+  if (d.a_kc ? (d.K % 32 != 0) : (d.M % 4 != 0)) return false;
+  if (d.b_kc ? (d.K % 32 != 0) : (d.N % 4 != 0)) return false;
   const bool conv = d.conv_T > 0;
   if (conv) {
-    if (d.conv_cin % 32 != 0 || d.conv_T < 128) return 0;
-    if (d.conv_on_b ? !tn : !d.a_kc) return 0;
-    if (tn && (long)d.K >= (1L << 24)) return 0;
+    if (d.conv_cin % 32 != 0 || d.conv_T < 128) return false;
+    if (d.conv_on_b ? !tn : !d.a_kc) return false;
+    if (tn && (long)d.K >= (1L << 24)) return false;
   }
   const long a_ext = d.a_kc ? ((long)(d.M + 128) * d.lda + d.K) : ((long)(d.K + 64) * d.lda + d.M);
   const long b_ext = d.b_kc ? ((long)(d.N + 128) * d.ldb + d.K) : ((long)(d.K + 64) * d.ldb + d.N);
-  if (a_ext * 4 >= 0x7FFF0000L || b_ext * 4 >= 0x7FFF0000L) return 0;
-  if (d.row_lens && !d.tile_map) return 0;                           // padded-row skipping needs the device-built schedule here
-  if (d.tile_map == reinterpret_cast<const int32_t*>(1)) return 0;
+  if (a_ext * 4 >= 0x7FFF0000L || b_ext * 4 >= 0x7FFF0000L) return false;
+  if (d.row_lens && !d.tile_map) return false;                           // padded-row skipping needs the device-built schedule here
+  if (d.tile_map == reinterpret_cast<const int32_t*>(1)) return false;
 
   int mt = tile_cfg / 10, nt = tile_cfg % 10;
   if (!((mt == 1 && nt == 1) || (mt == 1 && nt == 2) || (mt == 2 && nt == 2))) { mt = 1; nt = 1; }
@@ -542,17 +525,16 @@ static int sk_try(const ctts_gemm_desc& din, hipStream_t st, bool launch) {
   // ragged rows keep 64-row tiles: make the tile 256 columns wide instead (1 x 4 MFMA tiles per wave: the same 64 MFMAs per K-block and
   // barrier as the 128 x 128 tile, 5 fragment reads per 64 MFMAs instead of 6; 80 KB of LDS: exactly two workgroups per CU).  FFN conv
   // forward 491 -> 467 us, its data gradient 478 -> 457 us, fs2 step -1.05 % (same box); CTTS_SK_WIDE=0 keeps 64 x 128.
-  static const int wide = sk_env("CTTS_SK_WIDE", 1);
+  static const int wide = ctts_env_int("CTTS_SK_WIDE", 1);
   if (wide && mt == 1 && nt == 2 && d.a_kc && d.b_kc && d.N % 256 == 0) nt = 4;
   const int BM = 64 * mt, BN = 64 * nt;
-  SkArgs p;
   p.tiles_m = (d.M + BM - 1) / BM;
   p.tiles_n = (d.N + BN - 1) / BN;
   p.nkb = (d.K + 31) / 32;
   const long units = (long)p.tiles_m * p.tiles_n * p.nkb * mt * nt;  // in 64x64x32 equivalents
-  if (units < min_units || p.nkb < min_nkb) return 0;
+  if (units < min_units || p.nkb < min_nkb) return false;
   p.whole_tiles = p.nkb < split_from ? 1 : 0;
-  static const int chan_major = sk_env("CTTS_SK_CONV_ORDER", 1);      // 1: (channel block, tap) K order for conv views on A; 0: (tap, channel)
+  static const int chan_major = ctts_env_int("CTTS_SK_CONV_ORDER", 1);      // 1: (channel block, tap) K order for conv views on A; 0: (tap, channel)
   p.conv_chan_major = (conv && d.a_kc && !d.conv_on_b && chan_major && d.K % d.conv_cin == 0) ? 1 : 0;
   // ABI: split_k > 1 means "add alpha * A B to C" (plain read-modify-write by the tile's owner) - unless split_overwrite asks for C = ...
   p.accumulate = (d.split_k > 1 && !d.split_overwrite) ? 1 : 0;
@@ -576,20 +558,20 @@ static int sk_try(const ctts_gemm_desc& din, hipStream_t st, bool launch) {
   // a tile is cut in two (the owner gathers serially) - up to four pieces when every piece keeps a long reduction (>= 64 K-blocks: the
   // FFN weight gradient, 144 tiles x 512 K-blocks, measured 509 -> 494 us against the tile kernels with split-K atomics)
   const int cuts = (p.nkb >= 256 && max_split < 4) ? 4 : max_split;
-  if ((long)p.tiles_m * p.tiles_n * cuts < grid) return 0;
-  if (grid > SK_MAX_WG || (long)grid * BM * BN > SK_SLAB_FLOATS_MAX) return 0;
-  if (!launch) return 1;
+  if ((long)p.tiles_m * p.tiles_n * cuts < grid) return false;
+  if (grid > SK_MAX_WG || (long)grid * BM * BN > SK_SLAB_FLOATS_MAX) return false;
+  g.tile_m = BM; g.tile_n = BN;
+  g.grid = grid; g.stages = stages;
+  return true;
+}
+
+extern "C" int ctts_gemm_sk_launch(const ctts_gemm_desc& d, const SkArgs& p, const GemmGrid& g, hipStream_t st) {
+  const bool conv = d.conv_T > 0;
+  const int grid = g.grid, stages = g.stages, mt = g.tile_m / 64, nt = g.tile_n / 64;
   if (d.a_kc && d.b_kc) return conv ? sk_launch<true, true, true>(d, p, grid, stages, mt, nt, st) : sk_launch<true, true, false>(d, p, grid, stages, mt, nt, st);
   if (d.a_kc && !d.b_kc) return conv ? sk_launch<true, false, true>(d, p, grid, stages, mt, nt, st) : sk_launch<true, false, false>(d, p, grid, stages, mt, nt, st);
   return conv ? sk_launch<false, false, true>(d, p, grid, stages, mt, nt, st) : sk_launch<false, false, false>(d, p, grid, stages, mt, nt, st);
 }
 
-int ctts_gemm_sk_try(const ctts_gemm_desc& d, hipStream_t st) { return sk_try(d, st, true); }
-
-extern "C" int ctts_gemm_takes_persistent(const ctts_gemm_desc* d) {
-  if (!d) return 0;
-  ctts_gemm_desc c = *d;
-  if (c.nb0 < 1) c.nb0 = 1;
-  if (c.nb1 < 1) c.nb1 = 1;
-  return sk_try(c, nullptr, false) > 0 ? 1 : 0;
-}
+// the plan asked on its own: kernels that ctts_gemm asks earlier may still take the launch (gemm.hip gemm_route)
+extern "C" int ctts_gemm_takes_persistent(const ctts_gemm_desc* d) { return gemm_takes<SkArgs>(d, ctts_gemm_sk_plan); }

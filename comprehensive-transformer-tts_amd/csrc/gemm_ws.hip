@@ -19,7 +19,7 @@
 // Placement: workgroup b runs on XCD b % 8; the n-blocks that walk the same m-tiles are put on ONE XCD when that costs no extra round,
 // so an A tile is read from HBM / MALL once and from that XCD's L2 by the other n-blocks.
 // Padded-row skipping: the device-built 64-row tile schedule (ctts_row_tile_map) is walked instead of all tiles; inactive tiles are
-// zero-filled.  Eligibility: ctts_gemm_ws_try.
+// zero-filled.  Eligibility: ctts_gemm_ws_plan.
 #include "ctts_common.h"
 #include "gemm_common.h"
 #include <stdlib.h>
@@ -46,14 +46,6 @@ __device__ __forceinline__ void ws_dma16(ws_i32x4 rsrc, unsigned lds_addr, unsig
   asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
                :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc) : "memory");
 }
-
-struct WsArgs {
-  int tiles_m;         // ceil(M / 64)
-  int n_blocks;        // ceil(N / 128)
-  int wg_per_block;    // workgroups that share one 128-column block (grid = n_blocks * wg_per_block)
-  int xcd_aligned;     // 1: the n-blocks of one m-tile sequence sit on one XCD (wg_per_block % 8 == 0)
-  int debug;           // CTTS_WS_DEBUG: 1 = per-workgroup phase clocks into the tail of sk_ws, 2 = no epilogue, 4 = no in-loop DMA, 8 = no MFMA
-};
 
 // KB = K / 32 (compile time: the B fragments are a register array)
 template <int KB, bool B_KC, int ACT, bool DROP, bool BWD, bool AUX>
@@ -224,7 +216,7 @@ int ws_launch(const ctts_gemm_desc& d, const WsArgs& p, hipStream_t st) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL((gemm_ws_kernel<KB, B_KC, ACT, DROP, BWD, AUX>), dim3(p.n_blocks * p.wg_per_block), dim3(256), lds, st, d, p);
   CTTS_CHECK_LAUNCH("ctts_gemm(weight-stationary)");
-  return 1;
+  return 0;
 }
 
 template <int KB, bool B_KC, int ACT>
@@ -243,13 +235,8 @@ int ws_launch_layout(const ctts_gemm_desc& d, const WsArgs& p, hipStream_t st) {
     case 1: return ws_launch_act<KB, B_KC, 1>(d, p, st);
     case 2: return ws_launch_act<KB, B_KC, 2>(d, p, st);
     case 4: return ws_launch_act<KB, B_KC, 4>(d, p, st);
-    default: return 0;                                                 // tanh: no K = 256 linear uses it - the other kernels take it
+    default: ctts_set_error("ctts_gemm(weight-stationary): activation %d is not instantiated", d.act); return -1;      // (the plan refuses it)
   }
-}
-
-int ws_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
 }
 
 }  // namespace
@@ -257,18 +244,18 @@ int ws_env(const char* name, int dflt) {
 static int g_ws_enabled = -1;     // -1: take CTTS_WS (default on) at the first launch
 
 extern "C" int ctts_gemm_ws_enable(int on) {
-  const int prev = g_ws_enabled < 0 ? ws_env("CTTS_WS", 1) : g_ws_enabled;
+  const int prev = g_ws_enabled < 0 ? ctts_env_int("CTTS_WS", 1) : g_ws_enabled;
   g_ws_enabled = on ? 1 : 0;
   return prev;
 }
 
 // eligibility + grid of the weight-stationary kernel
-static bool ws_plan(const ctts_gemm_desc& d, WsArgs& p) {
-  if (g_ws_enabled < 0) g_ws_enabled = ws_env("CTTS_WS", 1) ? 1 : 0;
-  static const int min_rows = ws_env("CTTS_WS_MIN_ROWS", 4096);
-  static const int slots = ws_env("CTTS_WS_SLOTS", 512);          // 256 CUs x 2 workgroups
-  static const int align = ws_env("CTTS_WS_XCD_ALIGN", 1);
-  static const int debug = ws_env("CTTS_WS_DEBUG", 0);
+extern "C" bool ctts_gemm_ws_plan(const ctts_gemm_desc& d, WsArgs& p, GemmGrid& g) {
+  if (g_ws_enabled < 0) g_ws_enabled = ctts_env_int("CTTS_WS", 1) ? 1 : 0;
+  static const int min_rows = ctts_env_int("CTTS_WS_MIN_ROWS", 4096);
+  static const int slots = ctts_env_int("CTTS_WS_SLOTS", 512);          // 256 CUs x 2 workgroups
+  static const int align = ctts_env_int("CTTS_WS_XCD_ALIGN", 1);
+  static const int debug = ctts_env_int("CTTS_WS_DEBUG", 0);
   if (!g_ws_enabled) return false;
   if (d.nb0 * d.nb1 != 1 || (d.lens && (d.lim_m || d.lim_n || d.lim_k)) || d.E || d.split_k > 1 || d.conv_T > 0) return false;
   if (!d.a_kc || d.K != 256) return false;
@@ -281,7 +268,7 @@ static bool ws_plan(const ctts_gemm_desc& d, WsArgs& p) {
   // an output plane set (round 6) is written by the backward epilogue only, for whole 32-column K-blocks
   if (d.C_planes && (!d.epi_bwd || (d.ldc & 31) || (d.N & 31) || !al16(d.C_planes) || (long)(d.M + 64) * d.ldc * 6 >= 0x7FFF0000L)) return false;
   // combinations no K = 256 launch of the model uses are not compiled in: row scale, tanh, a pre-activation store without activation
-  if (d.rowscale || d.act == 3 || (d.Z && !d.act && !d.epi_bwd)) return false;
+  if (d.rowscale || (d.act != 0 && d.act != 1 && d.act != 2 && d.act != 4) || (d.Z && !d.act && !d.epi_bwd)) return false;
   if (d.tile_map == reinterpret_cast<const int32_t*>(1)) return false;
   p.tiles_m = (d.M + 63) / 64;
   p.n_blocks = (d.N + 127) / 128;
@@ -294,21 +281,13 @@ static bool ws_plan(const ctts_gemm_desc& d, WsArgs& p) {
   if (align && per8 >= 8 && per8 <= p.tiles_m && (p.tiles_m + per8 - 1) / per8 <= rounds) { per = per8; p.xcd_aligned = 1; }
   p.wg_per_block = per;
   p.debug = debug;
+  g.tile_m = 64; g.tile_n = 128;
   return true;
 }
 
-// 1 = launched, 0 = not eligible (the caller continues with the other kernels), < 0 error
-int ctts_gemm_ws_try(const ctts_gemm_desc& d, hipStream_t st) {
-  WsArgs p;
-  if (!ws_plan(d, p)) return 0;
+extern "C" int ctts_gemm_ws_launch(const ctts_gemm_desc& d, const WsArgs& p, const GemmGrid& g, hipStream_t st) {
   return d.b_kc ? ws_launch_layout<8, true>(d, p, st) : ws_launch_layout<8, false>(d, p, st);
 }
 
-extern "C" int ctts_gemm_takes_weight_stationary(const ctts_gemm_desc* dp) {
-  if (!dp) return 0;
-  ctts_gemm_desc d = *dp;
-  if (d.nb0 < 1) d.nb0 = 1;
-  if (d.nb1 < 1) d.nb1 = 1;
-  WsArgs p;
-  return ws_plan(d, p) ? 1 : 0;
-}
+// the plan asked on its own: the plane kernels are asked before it (gemm.hip gemm_route)
+extern "C" int ctts_gemm_takes_weight_stationary(const ctts_gemm_desc* d) { return gemm_takes<WsArgs>(d, ctts_gemm_ws_plan); }

@@ -12,7 +12,7 @@ void ctts_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* ctts_last_error(void) { return g_err; }
-extern "C" int ctts_version(void) { return 1; }
+extern "C" int ctts_version(void) { return 2; }
 
 namespace {
 

@@ -4,6 +4,7 @@ Tensors are only used for device memory + the current stream; every call goes th
 libctts_hip.so.  Inputs must live on a HIP device ("cuda" in PyTorch-ROCm) - a CPU tensor
 raises: there is no CPU path in the product.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -291,7 +292,7 @@ def _gemm_desc(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, a_off=0
     d.split_overwrite = int(bool(split_overwrite))
     if int(split_k) > 1 or a_planes is not None or ((SK_ENABLED if use_sk is None else use_sk) and nb0 * nb1 == 1 and M * N * K >= (1 << 24)):
         # split-K sums its pieces in a fixed order through the workspace (required); large unbatched GEMMs may run on the persistent
-        # stream-K kernel (the library decides: ctts_gemm_sk_try)
+        # stream-K kernel (the library decides: ctts_gemm_sk_plan)
         ws = gemm_workspace(A.device)
         d.sk_ws, d.sk_ws_bytes = ws.data_ptr(), ws.numel()
     return d
@@ -315,18 +316,30 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, defer=False, 
     return Cout
 
 
+GemmRoute = collections.namedtuple("GemmRoute", "kind tile_m tile_n split_k k_granule")
+
+
+def gemm_route(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, **kw):
+    """The kernel ctts_gemm would run these arguments on (include/ctts.h ctts_gemm_route; no launch): GemmRoute with kind = a name of
+    _lib.GEMM_KINDS, the workgroup tile, split_k as it will run and the K granule of a split.  Raises on what ctts_gemm would refuse."""
+    d, info = _gemm_desc(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc, **kw), _lib.GemmRouteInfo()
+    _lib.check(_lib.load().ctts_gemm_route(C.byref(d), C.byref(info)), "ctts_gemm_route")
+    return GemmRoute(_lib.GEMM_KINDS[info.kind], info.tile_m, info.tile_n, info.split_k, info.k_granule)
+
+
+def _gemm_takes(what, args, kw):
+    """the library's ctts_gemm_takes_<what> on the descriptor of gemm(*args, **kw) (no launch)"""
+    return bool(getattr(_lib.load(), "ctts_gemm_takes_" + what)(C.byref(_gemm_desc(*args, **kw))))
+
+
 def gemm_takes_persistent(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, **kw):
-    """True when ctts_gemm would run these arguments on the persistent stream-K kernel (no launch)."""
-    if not SK_ENABLED:
-        return False
-    d = _gemm_desc(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc, **kw)
-    return bool(_lib.load().ctts_gemm_takes_persistent(C.byref(d)))
+    """True when the persistent stream-K kernel is eligible for these arguments, asked on its own (gemm_route names the kernel that runs)."""
+    return SK_ENABLED and _gemm_takes("persistent", (A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc), kw)
 
 
 def gemm_takes_bf16_split(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, **kw):
     """True when ctts_gemm would run these arguments on the fp32-on-bf16-pipe kernel (six-term operand split; no launch)."""
-    d = _gemm_desc(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc, **kw)
-    return bool(_lib.load().ctts_gemm_takes_bf16_split(C.byref(d)))
+    return _gemm_takes("bf16_split", (A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc), kw)
 
 
 def gemm_bf16_split_enable(on):
@@ -353,12 +366,11 @@ def amp_split():
 
 def gemm_takes_planes(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, **kw):
     """True when ctts_gemm would run these arguments (a_planes / b_planes given) on the persistent plane kernel (no launch)."""
-    d = _gemm_desc(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc, **kw)
-    return bool(_lib.load().ctts_gemm_takes_planes(C.byref(d)))
+    return _gemm_takes("planes", (A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc), kw)
 
 
 def plane_shape_ok(M, N, K, conv_cin=None):
-    """Host-side pre-filter of the plane kernel's shape rules (csrc/gemm_pl.hip pl_try) - callers use it to decide whether splitting
+    """Host-side pre-filter of the plane kernel's shape rules (csrc/gemm_pl.hip ctts_gemm_pl_plan) - callers use it to decide whether splitting
     an operand is worth a launch; the library's answer (gemm_takes_planes) stays authoritative."""
     if not PLANES_ENABLED or BF16_SPLIT < 1 or not SK_ENABLED:
         return False
@@ -371,7 +383,7 @@ def plane_shape_ok(M, N, K, conv_cin=None):
 
 
 def plane_wgrad_shape_ok(Mo, No, Kred, cin=None):
-    """The same pre-filter for the weight-gradient plane kernel (csrc/gemm_plw.hip plw_try): output [Mo, No] = [cout, k * cin], reduction
+    """The same pre-filter for the weight-gradient plane kernel (csrc/gemm_plw.hip ctts_gemm_plw_plan): output [Mo, No] = [cout, k * cin], reduction
     over Kred (b, t) rows."""
     if not PLANES_ENABLED or not PLW_ENABLED or BF16_SPLIT < 1 or not SK_ENABLED:
         return False
@@ -441,9 +453,8 @@ def planes_piece(pl, q):
 
 
 def gemm_takes_weight_stationary(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, **kw):
-    """True when ctts_gemm would run these arguments on the weight-stationary K = 256 kernel (no launch)."""
-    d = _gemm_desc(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc, **kw)
-    return bool(_lib.load().ctts_gemm_takes_weight_stationary(C.byref(d)))
+    """True when the weight-stationary K = 256 kernel is eligible for these arguments, asked on its own (no launch)."""
+    return _gemm_takes("weight_stationary", (A, B, Cout, M, N, K, lda, ldb, ldc, a_kc, b_kc), kw)
 
 
 def gemm_ws_enable(on):

@@ -130,8 +130,25 @@ typedef struct ctts_gemm_desc {
 } ctts_gemm_desc;
 
 int ctts_gemm(const ctts_gemm_desc* d, void* stream);
-/* 1 (+ *count, *stride) when ctts_gemm would run `d` as a split-K launch whose partials the caller may keep (split_out); else 0. */
+/* 1 (+ *count, *stride) when ctts_gemm would run `d` as a split-K launch whose partials the caller may keep (split_out); else 0.
+ * For a descriptor with a K-contiguous A (NT / NN) the answer IGNORES A_planes / B_planes: the plane forward kernel takes split_k > 1
+ * with split_overwrite as a plain overwrite and writes no partials - do not defer such a launch (ask ctts_gemm_route). */
 int ctts_gemm_split_plan(const ctts_gemm_desc* d, int32_t* count, int64_t* stride);
+/* Which kernel ctts_gemm would run `d` on (csrc/gemm.hip gemm_route - the one place that orders the kernel families; no launch).  Same
+ * validation as ctts_gemm: an invalid descriptor gets its error (< 0), not a route.  tile_m x tile_n: the workgroup tile; split_k: the
+ * number of K ranges that write partial matrices, as it will run (lowered until the partials fit; 1 for every kernel that finishes its
+ * sum itself); k_granule: the multiple of K elements a split's range is rounded to.  kind NONE: M or N is 0, nothing is launched. */
+typedef enum ctts_gemm_kind {
+  CTTS_GEMM_NONE = 0,
+  CTTS_GEMM_PLANES, CTTS_GEMM_PLANES_WGRAD,          /* gemm_pl.hip, gemm_plw.hip: pre-split bf16 planes */
+  CTTS_GEMM_WEIGHT_STATIONARY,                       /* gemm_ws.hip: K = 256 */
+  CTTS_GEMM_X6,                                      /* gemm.hip: NT, operands split inside the kernel */
+  CTTS_GEMM_STREAM_K,                                /* gemm_sk.hip: persistent */
+  CTTS_GEMM_X6TN,                                    /* from here on: tile-per-workgroup kernels of gemm.hip (ordered split-K partials) */
+  CTTS_GEMM_SCALAR64, CTTS_GEMM_BUF128, CTTS_GEMM_BUF_K2, CTTS_GEMM_BUF_NARROW, CTTS_GEMM_BUF64, CTTS_GEMM_VEC128, CTTS_GEMM_VEC64
+} ctts_gemm_kind;
+typedef struct ctts_gemm_route_info { int32_t kind, tile_m, tile_n, split_k, k_granule; } ctts_gemm_route_info;
+int ctts_gemm_route(const ctts_gemm_desc* d, ctts_gemm_route_info* info);
 /* Data-gradient operands of many Conv1d layers in one launch: for every task dst[ci][kk][co] = src[co][k-1-kk][ci], src = the GEMM-major
  * forward weight [Cout][K][Cin] (what ctts_conv_weight_repack mode 4 does for one layer; 32 x 32 tiles through LDS, both sides
  * coalesced).  `tasks` is a HOST array.  The weights are constant during a step: trainer.TrainStep calls this once before the forward. */
@@ -163,14 +180,17 @@ const uint32_t* ctts_workspace_error_word(const void* ws);
 /* out[b] = XCC_ID (the XCD) workgroup b of an nblocks-wide launch ran on.  The persistent stream-K kernel assumes b % 8 (the default SPX
  * dispatch of an MI355X): callers verify once per device before handing ctts_gemm a workspace. */
 int ctts_xcd_probe(int32_t* out, int nblocks, void* stream);
-/* 1 when ctts_gemm would run this descriptor on the persistent stream-K kernel (sk_ws given, shape / alignment eligible, enough tiles
- * for the grid), else 0.  Callers that otherwise split the reduction (split_k > 1 + zero fill) ask first: the persistent kernel balances
- * the reduction itself and wants split_k = 1. */
+/* 1 when the persistent stream-K kernel is ELIGIBLE for this descriptor, asked on its own (sk_ws given, shape / alignment eligible,
+ * enough tiles for the grid), else 0 - kernels that ctts_gemm asks earlier (planes, weight-stationary, x6) may still take the launch:
+ * ctts_gemm_route names the kernel that runs.  Callers that otherwise split the reduction (split_k > 1 + zero fill) ask first: the
+ * persistent kernel balances the reduction itself and wants split_k = 1. */
 int ctts_gemm_takes_persistent(const ctts_gemm_desc* d);
 /* Switch for the weight-stationary K = 256 kernel (csrc/gemm_ws.hip; default on, env CTTS_WS=0 turns it off): returns the previous
  * setting.  Process-wide, not thread-safe - for parity tests and A/B timing (same descriptor on both kernel families). */
 int ctts_gemm_ws_enable(int on);
-/* 1 when ctts_gemm would run this descriptor on the weight-stationary kernel (no launch). */
+/* 1 when the weight-stationary kernel is ELIGIBLE for this descriptor, asked on its own (no launch; only the plane kernels are asked
+ * before it - ctts_gemm_route names the kernel that runs).  0 for an `act` outside 0 / 1 / 2 / 4: the kernel has no instantiation for
+ * tanh or for undefined codes (before ABI version 2 the answer for an undefined code was 1 although the tile kernels ran the launch). */
 int ctts_gemm_takes_weight_stationary(const ctts_gemm_desc* d);
 /* fp32 GEMM on the BF16 matrix pipe (ctts_gemm_desc.bf16_split >= 1; csrc/gemm.hip gemm_x6_kernel / gemm_x6tn_kernel, csrc/gemm_pl.hip
  * gemm_pl_kernel): large unbatched NT launches (both operands K-contiguous, conv view on A allowed, N a multiple of 128, split_k <= 1)
@@ -191,8 +211,9 @@ int ctts_gemm_takes_weight_stationary(const ctts_gemm_desc* d);
  *   - an infinite or NaN operand makes every output element it contributes to NON-FINITE (NaN where fp32 arithmetic would give
  *     +-inf: inf * 0-piece = NaN), elements it does not contribute to are unaffected - the finite / non-finite pattern of the result
  *     equals the fp32-MFMA kernels', which is what overflow diagnostics (isfinite checks, GradScaler) look at.
- * ctts_gemm_takes_bf16_split: 1 when ctts_gemm would run this descriptor on the in-kernel-split kernels (x6 / x6tn; no launch);
- * ctts_gemm_takes_planes: 1 when it would run it on a plane kernel (gemm_pl.hip: NT; gemm_plw.hip: TN). */
+ * Both read the route: ctts_gemm_takes_bf16_split: 1 when ctts_gemm WILL run this descriptor on the in-kernel-split kernels (kind X6 /
+ * X6TN; no launch); ctts_gemm_takes_planes: 1 when it will run it on a plane kernel (kind PLANES: NT; PLANES_WGRAD: TN).  Unlike
+ * ctts_gemm_route they do not validate the descriptor. */
 int ctts_gemm_takes_bf16_split(const ctts_gemm_desc* d);
 int ctts_gemm_takes_planes(const ctts_gemm_desc* d);
 /* Exact three-way bf16 split of fp32 matrices, many per launch: for every task and element (r, c), c < cols (cols % 32 == 0, ld % 32 == 0,

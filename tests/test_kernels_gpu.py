@@ -1417,3 +1417,58 @@ def _bf16_split_tn_body(conv, split, ragged, B_, T, Cin, ks, Mo, Kred, No, lens,
     # both accumulate 4,096+ products per output in fp32; the fp32-MFMA path cuts that chain (stream-K / split-K pieces summed
     # afterwards), so its rounding error is somewhat smaller on unsplit launches - the products themselves are exact either way (above)
     assert e6 <= 2.5 * e32 + 1e-6, (e6, e32)
+
+
+def _route_unit(M, N, Kd, g):              # test_gemm_nt's operands
+    return torch.rand(M, Kd, generator=g) * 2 - 1, torch.rand(N, Kd, generator=g) * 2 - 1
+
+
+def _route_exact(M, N, Kd, g):             # 18-bit integers against sparse +-1: every fp32 partial sum is an exact integer
+    big = torch.randint(-(1 << 17), (1 << 17) + 1, (M, Kd), generator=g).float()
+    return big, (torch.randint(-1, 2, (N, Kd), generator=g) * (torch.rand(N, Kd, generator=g) < 1 / 64)).float()
+
+
+# kind, layout, M, N, K, operands [M, K] x [N, K], keyword arguments, bound on max |C - float64| given max |float64| - each the bound of
+# the family's own test on that operand distribution (named on the line)
+_ROUTE_CASES = [
+    ("scalar64", "NT", 70, 50, 30, _route_unit, {}, lambda s: 2e-6 * max(1, 30 / 16) * max(1.0, s)),           # test_gemm_nt
+    ("buf64", "NT", 130, 130, 64, _route_unit, {}, lambda s: 2e-6 * max(1, 64 / 16) * max(1.0, s)),            # test_gemm_nt
+    ("buf_k2", "NT", 256, 64, 256, _route_unit, {}, lambda s: 2e-6 * max(1, 256 / 16) * max(1.0, s)),          # test_gemm_nt
+    ("buf_narrow", "NT", 256, 32, 64, _route_unit, {}, lambda s: 2e-6 * max(1, 64 / 16) * max(1.0, s)),        # test_gemm_nt
+    ("x6", "NT", 1024, 128, 256, _route_exact, dict(bf16_split=2), lambda s: 0.0),                             # test_bf16_split_gemm_is_exact_...
+    ("x6tn", "TN", 128, 128, 2048, _route_exact, dict(bf16_split=2, split_k=2), lambda s: 0.0),                # test_bf16_split_weight_gradient_...
+    ("weight_stationary", "NT", 4096, 64, 256,                                                                 # test_weight_stationary_gemm_...
+     lambda M, N, Kd, g: (torch.randn(M, Kd, generator=g), torch.randn(N, Kd, generator=g) * 0.05), {}, lambda s: 2e-5 * max(1.0, s)),
+    ("planes", "NT", 128, 256, 64, _route_unit, dict(bf16_split=2, planes=True), lambda s: 2e-5 * max(1.0, s)),        # test_planes_gpu: ..._vs_fp64
+    ("planes_wgrad", "TN", 128, 256, 64, _route_unit, dict(bf16_split=2, split_k=2, planes=True), lambda s: 2e-6 * s),  # test_planes_wgrad_gpu close()
+    ("stream_k", "NT", 4096, 1024, 2048,                                                                       # test_dominant_stream_k_kernel_vs_fp64_...
+     lambda M, N, Kd, g: (torch.rand(M, Kd, generator=g) - 0.5, (torch.rand(N, Kd, generator=g) - 0.5) * 0.1), dict(bf16_split=0), lambda s: 2e-5),
+]
+
+
+@pytest.mark.parametrize("kind,layout,M,N,Kd,make,kw,bound", _ROUTE_CASES, ids=[c[0] for c in _ROUTE_CASES])
+def test_every_route_kind_names_the_kernel_that_runs_the_launch(kind, layout, M, N, Kd, make, kw, bound):
+    """K.gemm_route names `kind` for the descriptor, and the launch of the same descriptor computes the product: binds every route kind
+    that a small launch reaches to its launcher (the vec kinds need an operand beyond 2 GiB, buf128 a tuning knob: tests/test_gemm_route_cpu.py)."""
+    g = torch.Generator().manual_seed(41)
+    A, Bm = make(M, N, Kd, g)
+    ref = A.double() @ Bm.double().t()
+    kw = dict(kw)
+    if layout == "TN":                       # C = A'^T B' with A' = A^T [K, M], B' = B^T [K, N]; split_k > 1 adds into C
+        dA, dB, out = A.t().contiguous().to(DEV), Bm.t().contiguous().to(DEV), torch.zeros(M, N, device=DEV)
+        args = (dA, dB, out, M, N, Kd, M, N, N, False, False)
+    else:
+        dA, dB, out = A.to(DEV), Bm.to(DEV), torch.full((M, N), float("nan"), device=DEV)
+        args = (dA, dB, out, M, N, Kd, Kd, Kd, N, True, True)
+    if kw.pop("planes", False):
+        kw["a_planes"], kw["b_planes"] = K.split_planes([dA, dB])
+    route = K.gemm_route(*args, **kw)
+    assert route.kind == kind, route
+    K.gemm(*args, **kw)
+    torch.cuda.synchronize()
+    assert _sk_error_word() == 0
+    err, scale = float((out.double().cpu() - ref).abs().max()), float(ref.abs().max())
+    print(f"{kind}: max |err| vs fp64 {err:.3e} (|ref| max {scale:.3e}, bound {bound(scale):.3e})")
+    if kind in ("x6", "x6tn"):
+        assert scale < 2 ** 24
+    assert err <= bound(scale), (err, bound(scale))

@@ -158,7 +158,7 @@ def test_weight_gradient_plane_kernel_loops_hold_only_dma_transpose_reads_and_mf
 
 
 def test_weight_gradient_plane_prefilter():
-    """kernels.plane_wgrad_shape_ok mirrors plw_try's shape rules (the library's answer stays authoritative on the GPU)"""
+    """kernels.plane_wgrad_shape_ok mirrors ctts_gemm_plw_plan's shape rules (the library's answer stays authoritative on the GPU)"""
     from ctts_amd import kernels as K
     prev = K.gemm_bf16_split_enable(True)
     try:
