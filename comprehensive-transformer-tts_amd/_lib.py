@@ -211,6 +211,9 @@ _SIGNATURES = {
     "ctts_trim_silence": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _f32, C.c_int, C.c_int, _vp],
     "ctts_attn_prior": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _i64, _i64, _f32, _vp],
     "ctts_outlier_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp],
+    "ctts_mel_cepstrum": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "ctts_dtw": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "ctts_path_metrics": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "ctts_comm_unique_id": [_vp],
     "ctts_comm_create": [C.POINTER(_vp), _i32, _i32, _vp],
     "ctts_comm_destroy": [_vp],
@@ -221,7 +224,8 @@ EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["ctts_last_error", "ctts_version"
                                                "ctts_mel_spectrogram_workspace_bytes", "ctts_gemm_workspace_bytes", "ctts_workspace_bytes",
                                                "ctts_workspace_error_word", "ctts_fastformer_workspace_floats",
                                                "ctts_griffinlim_workspace_bytes", "ctts_griffinlim_state_floats",
-                                               "ctts_pitch_track_workspace_bytes", "ctts_trim_silence_workspace_bytes"])
+                                               "ctts_pitch_track_workspace_bytes", "ctts_trim_silence_workspace_bytes",
+                                               "ctts_dtw_workspace_bytes"])
 ADAM_STATE_FLOATS = 3 + 2048          # CTTS_ADAM_STATE_FLOATS of include/ctts.h
 ABI_VERSION = 2                       # ctts_version() of the library this binding was written for
 
@@ -274,6 +278,8 @@ def load():
     lib.ctts_pitch_track_workspace_bytes.argtypes = []
     lib.ctts_trim_silence_workspace_bytes.restype = C.c_size_t
     lib.ctts_trim_silence_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.ctts_dtw_workspace_bytes.restype = C.c_size_t
+    lib.ctts_dtw_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ctts_relmha_workspace_floats.restype = C.c_size_t
     lib.ctts_relmha_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int]
     _lib = lib

@@ -1743,3 +1743,83 @@ def outlier_stats(values, lens):
     _lib.check(_lib.load().ctts_outlier_stats(_p(values), _p(lens), _p(keep), _p(count), _p(s), _p(m2), _p(lo), _p(hi), B, L, _stream()),
                "ctts_outlier_stats")
     return keep, count, s, m2, lo, hi
+
+
+# ---- objective evaluation: mel cepstrum, DTW, path metrics (csrc/metrics.hip) -------------------------------------------------------
+CEPSTRUM_MAX_COEF = 32
+DTW_MAX_FRAMES = 2048
+DTW_ALIGN = {"dtw": 0, "none": 1}
+
+
+def mel_cepstrum(mel, frames=None, n_coef=13):
+    """mel [B,n_mel,F] float32 (natural-log mel), frames int32 [B] or None -> cepstra [B,F,n_coef] (DCT-II coefficients 1 .. n_coef)"""
+    if not torch.is_tensor(mel) or mel.dim() != 3:
+        raise _lib.CttsError("mel_cepstrum: expected mel [B, n_mel, F]")
+    _p(mel)
+    _al4(_f32c(mel, "mel"), "mel")
+    B, M, F = mel.shape
+    n_coef = int(n_coef)
+    if B < 1 or F < 1:
+        raise _lib.CttsError(f"mel_cepstrum: empty batch {tuple(mel.shape)}")
+    if not (1 <= n_coef <= CEPSTRUM_MAX_COEF and n_coef < M):
+        raise _lib.CttsError(f"mel_cepstrum: need 1 <= n_coef <= {CEPSTRUM_MAX_COEF} and n_coef < n_mel = {M}, got {n_coef}")
+    if frames is not None:
+        _lens_i32(frames, B, "mel_cepstrum")
+    out = torch.empty(B, F, n_coef, dtype=torch.float32, device=mel.device)
+    _lib.check(_lib.load().ctts_mel_cepstrum(_p(mel), _p(frames), _p(out), B, M, F, n_coef, _stream()), "ctts_mel_cepstrum")
+    return out
+
+
+def dtw(x, x_lens, y, y_lens, align="dtw"):
+    """x [B,Tx,K], y [B,Ty,K] float32, x_lens / y_lens int32 [B] -> (cost [B], path_len int32 [B], path int32 [B, Tx + Ty - 1, 2]);
+    align "dtw" or "none" (frame i against frame i).  Padded Tx, Ty <= 2048: refused before any launch otherwise."""
+    if not torch.is_tensor(x) or not torch.is_tensor(y) or x.dim() != 3 or y.dim() != 3:
+        raise _lib.CttsError("dtw: expected x [B, Tx, K] and y [B, Ty, K]")
+    _p(x), _p(y)
+    _al4(_f32c(x, "x"), "x"), _al4(_f32c(y, "y"), "y")
+    if align not in DTW_ALIGN:
+        raise _lib.CttsError(f"dtw: align {align!r}: expected 'dtw' or 'none'")
+    B, Tx, K = x.shape
+    Ty = y.shape[1]
+    if y.shape[0] != B or y.shape[2] != K:
+        raise _lib.CttsError(f"dtw: x {tuple(x.shape)} against y {tuple(y.shape)}")
+    if B < 1 or Tx < 1 or Ty < 1:
+        raise _lib.CttsError(f"dtw: empty batch {tuple(x.shape)} / {tuple(y.shape)}")
+    if Tx > DTW_MAX_FRAMES or Ty > DTW_MAX_FRAMES:
+        raise _lib.CttsError(f"dtw: padded lengths {Tx} x {Ty} exceed {DTW_MAX_FRAMES} frames per side")
+    if not 1 <= K <= CEPSTRUM_MAX_COEF:
+        raise _lib.CttsError(f"dtw: K = {K} outside [1, {CEPSTRUM_MAX_COEF}]")
+    _lens_i32(x_lens, B, "dtw")
+    _lens_i32(y_lens, B, "dtw")
+    dev = x.device
+    lib = _lib.load()
+    ws = torch.empty(lib.ctts_dtw_workspace_bytes(B, Tx, Ty) // 4, dtype=torch.int32, device=dev) if align == "dtw" else None
+    cost = torch.empty(B, dtype=torch.float32, device=dev)
+    path_len = torch.empty(B, dtype=torch.int32, device=dev)
+    path = torch.empty(B, Tx + Ty - 1, 2, dtype=torch.int32, device=dev)
+    _lib.check(lib.ctts_dtw(_p(x), _p(y), _p(x_lens), _p(y_lens), _p(ws), _p(cost), _p(path_len), _p(path), B, Tx, Ty, K, DTW_ALIGN[align],
+                            _stream()), "ctts_dtw")
+    return cost, path_len, path
+
+
+def path_metrics(path, path_len, f0_x, f0_y):
+    """path int32 [B,P,2], path_len int32 [B], f0_x [B,Tx], f0_y [B,Ty] Hz (0 = unvoiced) -> float64 [B,4]: pairs, pairs voiced in both,
+    sum of squared log-F0 differences in cents over those, pairs whose voicing differs"""
+    if not torch.is_tensor(path) or path.dim() != 3 or path.shape[2] != 2:
+        raise _lib.CttsError("path_metrics: expected path [B, P, 2]")
+    _p(path)
+    if path.dtype != torch.int32 or not path.is_contiguous():
+        raise _lib.CttsError("path_metrics: path must be a contiguous int32 tensor")
+    B, P, _ = path.shape
+    if B < 1 or P < 1:
+        raise _lib.CttsError(f"path_metrics: empty path {tuple(path.shape)}")
+    _lens_i32(path_len, B, "path_metrics")
+    for t, name in ((f0_x, "f0_x"), (f0_y, "f0_y")):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1:
+            raise _lib.CttsError(f"path_metrics: expected {name} [B, T] with B = {B}")
+        _p(t)
+        _al4(_f32c(t, name), name)
+    out = torch.empty(B, 4, dtype=torch.float64, device=path.device)
+    _lib.check(_lib.load().ctts_path_metrics(_p(path), _p(path_len), _p(f0_x), _p(f0_y), _p(out), B, f0_x.shape[1], f0_y.shape[1], P, _stream()),
+               "ctts_path_metrics")
+    return out

@@ -823,6 +823,40 @@ int ctts_attn_prior(const int32_t* src_lens, const int32_t* mel_lens, float* out
 int ctts_outlier_stats(const float* values, const int32_t* lens, uint8_t* keep, int32_t* count, double* sum, double* m2, float* vmin,
                        float* vmax, int B, int L, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Objective evaluation on the device (csrc/metrics.hip): mel-cepstral distortion after dynamic-time-warping
+ * alignment, log-F0 RMSE and voiced / unvoiced error of a synthesised utterance against its recording.  fp32 data, lengths are int32
+ * device arrays, read once per workgroup and clamped to [0, padded size]; rows at or beyond a length are never read (they may hold
+ * NaN).  Stream-ordered, no allocation, no host sync, no float atomics: every sum has one fixed order, bit-identical run to run.
+ *
+ * ctts_mel_cepstrum: mel [B][n_mel][F] (natural-log mel, the layout ctts_mel_spectrogram writes), frames [B] (NULL = F) ->
+ * out [B][F][n_coef], out[b][f][k-1] = sqrt(2/M) sum_m mel[b][m][f] cos(pi k (m + 1/2) / M) for k = 1 .. n_coef, M = n_mel: the
+ * orthonormal DCT-II over the mel axis with coefficient 0 dropped, terms added in channel order.  Rows f >= frames[b] are written as
+ * zeros.  These are the DCT of THIS project's log-mel (MFCC-style cepstra), not WORLD / SPTK mel-cepstra.
+ * DOMAIN: 1 <= n_coef <= 32, n_coef < n_mel, n_mel n_coef <= 12288, B <= 65535.
+ *
+ * ctts_dtw: x [B][Tx][K], y [B][Ty][K], x_lens / y_lens [B] -> cost [B], path_len [B], path [B][Tx + Ty - 1][2].
+ *   align = 0: dynamic time warping.  Local cost d(i,j) = ||x_i - y_j||_2 (not squared); A(i,j) = d(i,j) + min(A(i-1,j-1), A(i-1,j),
+ *   A(i,j-1)), A(0,0) = d(0,0); no window, no slope weights.  cost[b] = A(Lx-1, Ly-1).  The path is walked back from (Lx-1, Ly-1).
+ *   TIE RULE: the diagonal (i-1,j-1) wins when it is <= both others, then (i-1,j), then (i,j-1).
+ *   align = 1: no warping - frame i against frame i for i < min(Lx, Ly); cost[b] = sum_i d(i,i), the path is (i,i).
+ *   path holds (i, j) pairs in order from (0,0); the first path_len[b] rows are filled and the kernel writes -1 into every other row.
+ *   Lx = 0 or Ly = 0 gives cost 0, path_len 0 and an all -1 path.
+ *   workspace: ctts_dtw_workspace_bytes(B, Tx, Ty) bytes, 32-byte aligned (the local costs as floats, one anti-diagonal per row of
+ *   roundup(Tx, 8): [B][Tx + Ty - 1][roundup(Tx, 8)], then two direction bits per cell); align = 1 does not touch it (NULL allowed).
+ *   DOMAIN: 1 <= Tx, Ty <= 2048 (padded sizes; refused before any launch otherwise), 1 <= K <= 32, B <= 65535.
+ *
+ * ctts_path_metrics: path [B][P][2], path_len [B] (clamped to P), f0_x [B][Tx], f0_y [B][Ty] in Hz with 0 = unvoiced (voiced: > 0) ->
+ * out [B][4] double: the number of aligned pairs, the number voiced in both signals, the sum over those of
+ * (1200 log2(f0_x[i] / f0_y[j]))^2 (cents squared, evaluated in double), the number of pairs whose voicing differs.  A row of the
+ * path outside [0,Tx) x [0,Ty) is no pair and is skipped. */
+size_t ctts_dtw_workspace_bytes(int B, int Tx, int Ty);
+int ctts_mel_cepstrum(const float* mel, const int32_t* frames, float* out, int B, int n_mel, int F, int n_coef, void* stream);
+int ctts_dtw(const float* x, const float* y, const int32_t* x_lens, const int32_t* y_lens, void* workspace, float* cost, int32_t* path_len,
+             int32_t* path, int B, int Tx, int Ty, int K, int align, void* stream);
+int ctts_path_metrics(const int32_t* path, const int32_t* path_len, const float* f0_x, const float* f0_y, double* out, int B, int Tx, int Ty,
+                      int P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,12 @@ the whole call plain x 60 against momentum M x --iters (default 32), the spectra
 the smallest iteration count at which momentum reaches the plain loop's convergence after 60, and with --device-phase the wall time of
 a default angles=None call (host draw + copy) against a seed= call (phase drawn by the kernel).
 
-    python tools/bench_griffinlim.py --momentum 0.99 --iters 32 --device-phase --out profiles/griffinlim_fast_bench.json"""
+    python tools/bench_griffinlim.py --momentum 0.99 --iters 32 --device-phase --out profiles/griffinlim_fast_bench.json
+
+--quality (opt-in, both reports) adds the mel-cepstral distortion (ctts_amd.metrics, MFCC-style: the DCT of this project's log-mel, not
+WORLD / SPTK mel-cepstra) of each Griffin-Lim output, its log-mel re-extracted by `TacotronSTFT`, against the log-mel of the magnitudes
+it was given, frame by frame (align="none"); with --momentum also of the fast output against the plain one (`compare_wavs`).  Without
+the flag the output is unchanged."""
 import argparse
 import json
 import os
@@ -72,6 +77,17 @@ def kernel_us(fn, name):
             tot += getattr(e, "device_time_total", None) or getattr(e, "cuda_time_total", 0.0)
             cnt += e.count
     return tot / cnt if cnt else None
+
+
+def mcd_vs_input(mag, frame_lens, sig):
+    """mag [B,513,F] (what Griffin-Lim was given), frame_lens [B], sig [B, 256 (F - 1)] -> MCD dB (path_len-weighted) of the signal's
+    re-extracted log-mel against log(clamp(mel_basis mag)), frame i against frame i"""
+    from ctts_amd import metrics as M
+    tac = audio.TacotronSTFT(NFFT, HOP, NFFT, 80, SR, 0, 8000).to(mag.device)
+    mel_in = audio.dynamic_range_compression(torch.matmul(tac.mel_basis, mag)).contiguous()
+    fl = torch.as_tensor(frame_lens, dtype=torch.int32).to(mag.device)
+    mel, frames, _ = M.wav_features(sig, HOP * (fl - 1), tac)
+    return round(M.summarize(M.compare_mels(mel_in, fl, mel, frames, align="none"))["mcd_db"].item(), 4)
 
 
 def rel_l2(a, b):
@@ -166,6 +182,15 @@ def fast_report(a):
                      "speedup": round(plain_ms / fast_ms, 2)},
            "convergence_by_iterations": curve,
            "momentum_iters_to_reach_plain_60": match}
+    if a.quality:
+        from ctts_amd import metrics as M
+        tac = audio.TacotronSTFT(NFFT, HOP, NFFT, 80, SR, 0, 8000).to(dev)
+        sl = torch.tensor(samples, dtype=torch.int32, device=dev)
+        r = M.summarize(M.compare_wavs(plain_out, sl, fast_out, sl, tac, align="none"))
+        res["quality"] = {"plain_mcd_db_vs_input_mel": mcd_vs_input(mag, lens, plain_out),
+                          "momentum_mcd_db_vs_input_mel": mcd_vs_input(mag, lens, fast_out),
+                          "momentum_vs_plain": {"mcd_db": round(r["mcd_db"].item(), 5), "lf0_rmse_cents": r["lf0_rmse_cents"].item(),
+                                                "vuv_error": r["vuv_error"].item(), "n_voiced": int(r["n_voiced"].item())}}
     if a.device_phase:
         wsteps = max(1, min(a.steps, 5))
         host_ms = wall_ms(lambda: audio.griffin_lim(mag, stft, ITERS, lens=lens_d), wsteps, 1)
@@ -194,6 +219,7 @@ def main():
     ap.add_argument("--momentum", type=float, default=None, help="report on fast Griffin-Lim with this momentum (e.g. 0.99) instead")
     ap.add_argument("--iters", type=int, default=None, help="with --momentum: iterations of the momentum loop (default 32; plain runs 60)")
     ap.add_argument("--device-phase", action="store_true", help="with --momentum: time an angles=None call against a seed= call")
+    ap.add_argument("--quality", action="store_true", help="add the mel-cepstral distortion of the outputs (see the module docstring)")
     a = ap.parse_args()
     if a.momentum is None and (a.iters is not None or a.device_phase):
         ap.error("--iters and --device-phase belong to the --momentum report")
@@ -243,6 +269,8 @@ def main():
             "stock_torch_per_utterance": {"ms": round(st_ms, 3), "audio_s_per_s": round(audio_s / (st_ms / 1e3), 1)},
             "speedup_vs_padded_batch": round(stp_ms / nat_ms, 2), "speedup_vs_per_utterance": round(st_ms / nat_ms, 2),
             "max_rel_l2_vs_stock": max(diffs)}
+        if a.quality:
+            res["shapes"][name]["quality"] = {"native_mcd_db_vs_input_mel": mcd_vs_input(mag, lens, nat)}
     line = json.dumps(res)
     print(line)
     if a.out:

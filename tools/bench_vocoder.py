@@ -21,7 +21,13 @@ ragged forward does not skip.
 at both shapes: the native fp16 mode, the native fp32 mode and stock torch fp16 (the restatement's F.conv1d / F.conv_transpose1d on the
 same folded weights after .half(), MIOpen), interleaved and repeated like --ragged; with --ragged also both native modes with `lens` on
 the canonical batch.  Reported: the ratios, the per-stage ms of both native modes and the wav error (max, rms) of both half paths
-against the native fp32 output."""
+against the native fp32 output.
+
+--quality (opt-in; the plain and the --precision fp16 report) adds a "quality" entry per shape: the mel-cepstral distortion
+(ctts_amd.metrics, MFCC-style: the DCT of this project's log-mel, not WORLD / SPTK mel-cepstra) of each native output, its log-mel
+re-extracted by `TacotronSTFT`, against the input mel's own cepstra frame by frame (align="none"), and with --precision fp16 of the fp16
+output against the fp32 output (`compare_wavs`).  The weights here are random, so the first figure says what the network does to a
+mel, not how a trained vocoder sounds; the second is the distance between the two modes.  Without the flag the output is unchanged."""
 import argparse
 import json
 import os
@@ -59,6 +65,24 @@ def v1_generator(dev):
     g.eval()
     g.remove_weight_norm()                      # utils/model.py:66
     return g.to(dev)
+
+
+def quality(view, wavs):
+    """view [B,80,T] (the input mel), wavs {name: [B,1,256 T]} -> {name: MCD dB against the input mel (path_len-weighted)}, plus the
+    MCD between the first two outputs when there are two; frame i against frame i"""
+    from ctts_amd import audio, metrics as M
+    stft = audio.TacotronSTFT(1024, HOP, 1024, 80, SR, 0, 8000).to(view.device)
+    mel_in = view.float().contiguous()
+    out = {}
+    for name, w in wavs.items():
+        mel, frames, _ = M.wav_features(w[:, 0], None, stft)
+        out[f"{name}_mcd_db_vs_input_mel"] = round(M.summarize(M.compare_mels(mel_in, None, mel, frames, align="none"))["mcd_db"].item(), 4)
+    names = list(wavs)
+    if len(names) >= 2:
+        r = M.summarize(M.compare_wavs(wavs[names[0]][:, 0], None, wavs[names[1]][:, 0], None, stft, align="none"))
+        out[f"{names[1]}_vs_{names[0]}"] = {"mcd_db": round(r["mcd_db"].item(), 5), "lf0_rmse_cents": r["lf0_rmse_cents"].item(),
+                                           "vuv_error": r["vuv_error"].item(), "n_voiced": int(r["n_voiced"].item())}
+    return out
 
 
 def timed(fn, steps, warmup, stages):
@@ -211,6 +235,9 @@ def half_main(a, dev, g, mel_lens):
             sh["valid_frames"], sh["padded_frames"] = sum(mel_lens), B * T
         sh["stage_ms"] = {k: {"fp16": st16[k], "fp32": st32[k], "ratio": round(st32[k] / st16[k], 3)} for k in st16}
         sh["wav_error_vs_native_fp32"] = err
+        if a.quality:
+            with torch.no_grad():
+                sh["quality"] = quality(view, {"native_fp32": g(view, precision="fp32"), "native_fp16": g(view, precision="fp16")})
         res["shapes"][name] = sh
     line = json.dumps(res)
     print(line)
@@ -231,6 +258,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--parent", default=None)
     ap.add_argument("--precision", choices=("fp32", "fp16"), default="fp32")
+    ap.add_argument("--quality", action="store_true", help="add the mel-cepstral distortion of the outputs (see the module docstring)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = v1_generator(dev)
@@ -274,6 +302,8 @@ def main():
             "stock_torch_fp32": {"ms": round(st_ms, 3), "audio_s_per_s": round(audio_s / (st_ms / 1e3), 1),
                                  "tflops": round(flop / st_ms / 1e9, 1), "frac_of_416.7TF": round(flop / st_ms / 1e9 / PEAK_TF, 3), "stage_ms": st_st},
             "speedup": round(st_ms / nat_ms, 2), "max_abs_diff": diff}
+        if a.quality:
+            res["shapes"][name]["quality"] = quality(view, {"native_fp32": nat})
     line = json.dumps(res)
     print(line)
     if a.out:
