@@ -199,6 +199,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------- BatchNorm1d (channel-last)
+// Does var = E[x^2] - mean^2 of these sums (n rows) cancel more than float partial sums can afford?  With float partials the relative
+// error of rstd was measured at 7.6e-8 * (1 + mean^2 / var) (7.6e-7 at a channel mean of 3 std, [150, 80]); up to mean^2 = 5 var that stays
+// inside 4 * 2^-23, the rounding of the float rstd itself and of the eps add.  Also true when the difference comes out <= 0.
+__device__ __forceinline__ bool colstats_cancels(double sum_x, double sum_xx, double n) {
+  const double mu = sum_x / n;
+  return !(mu * mu <= 5.0 * (sum_xx / n - mu * mu));
+}
+
 // column sums: block = 64 columns x a stripe of rows; thread (c = tid & 63, ty = tid >> 6)
 template <int MODE>  // 0: sum x, sum x^2   1: BN-bwd sums (dt, dt*xhat)
 __global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict__ x, const float* __restrict__ dy,
@@ -209,12 +217,20 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict_
                                                          unsigned char* ws, int G) {
   // C is the row width of the (possibly folded) view: a narrow matrix [R, creal] with creal < 64 is read as [R/k, k*creal] so that
   // all 64 lanes of a wave carry data; column c of the view is channel c % creal.
+  // MODE 0 keeps two pairs of partials: the float pair, and a double pair with the square formed in double.  bn_finalize takes
+  // var = E[x^2] - mean^2 of the sums, and the float partials lose mean^2 / var of their 24 bits there (a channel mean of 30 std: rstd
+  // off by 5e-5).  colstats_cancels decides per channel: the elected workgroup hands out the float pair where it is
+  // accurate - those sums, and everything trained on them, stay what they were - and the double pair elsewhere.  Both are summed in
+  // the same fixed order, so either is bit-reproducible.
+  constexpr int NV = MODE == 0 ? 4 : 2;
   __shared__ float s1[4][64], s2[4][64];
+  __shared__ double sd1[4][64], sd2[4][64];
   const int c = blockIdx.x * 64 + (threadIdx.x & 63), ty = threadIdx.x >> 6;
   const int ch = c % creal;
   const int stripe = (rows + gridDim.y - 1) / gridDim.y;
   const int r0 = blockIdx.y * stripe, r1 = min(rows, r0 + stripe);
   float a = 0.f, b = 0.f;
+  double ad = 0.0, bd = 0.0;
   if (c < C) {
     float mu = 0.f, rs = 1.f, g = 1.f, be = 0.f, inv_keep = 1.f;
     uint32_t dkey = 0;
@@ -224,7 +240,7 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict_
 #pragma unroll 4
     for (int r = r0 + ty; r < r1; r += 4) {
       const float xv = x[(long)r * C + c];
-      if (MODE == 0) { a += xv; b += xv * xv; }
+      if (MODE == 0) { a += xv; b += xv * xv; const double xd = (double)xv; ad += xd; bd += xd * xd; }
       else {
         float d = dy[(long)r * C + c];
         if (do_drop) d *= ctts_drop_scale(dkey, (uint32_t)r * (uint32_t)C + (uint32_t)c, p_drop, inv_keep);
@@ -235,29 +251,50 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict_
     }
   }
   s1[ty][threadIdx.x & 63] = a; s2[ty][threadIdx.x & 63] = b;
+  if (MODE == 0) { sd1[ty][threadIdx.x & 63] = ad; sd2[ty][threadIdx.x & 63] = bd; }
   __syncthreads();
-  double tot[2] = {0.0, 0.0};
+  double tot[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) tot[k] = 0.0;
   if (ty == 0) {
     const int l = threadIdx.x;
     tot[0] = (double)s1[0][l] + s1[1][l] + s1[2][l] + s1[3][l];
     tot[1] = (double)s2[0][l] + s2[1][l] + s2[2][l] + s2[3][l];
+    if (MODE == 0) {
+      tot[NV - 2] = sd1[0][l] + sd1[1][l] + sd1[2][l] + sd1[3][l];
+      tot[NV - 1] = sd2[0][l] + sd2[1][l] + sd2[2][l] + sd2[3][l];
+    }
   }
-  if (!ctts_ordered_colsum<double, 2>(tot, ws, blockIdx.x, blockIdx.y, gridDim.y, G)) return;
+  if (!ctts_ordered_colsum<double, NV>(tot, ws, blockIdx.x, blockIdx.y, gridDim.y, G)) return;
   // the elected workgroup of this column block WRITES the sums (no zero fill, no atomics); a folded view (C = k * creal <= 64, one column
   // block) first adds the k copies of a channel in index order
+  const double n = (double)rows * (double)(C / creal);        // rows of the unfolded matrix
   if (C != creal) {
-    __shared__ double sf[2][64];
-    if (ty == 0) { sf[0][threadIdx.x] = c < C ? tot[0] : 0.0; sf[1][threadIdx.x] = c < C ? tot[1] : 0.0; }
+    __shared__ double sf[NV][64];
+    if (ty == 0) {
+#pragma unroll
+      for (int k = 0; k < NV; ++k) sf[k][threadIdx.x] = c < C ? tot[k] : 0.0;
+    }
     __syncthreads();
     if (ty == 0 && threadIdx.x < creal) {
-      double a = 0.0, b = 0.0;
-      for (int j = threadIdx.x; j < C; j += creal) { a += sf[0][j]; b += sf[1][j]; }
-      sums[threadIdx.x] = a;
-      sums[creal + threadIdx.x] = b;
+      double f[NV];
+#pragma unroll
+      for (int k = 0; k < NV; ++k) f[k] = 0.0;
+      for (int j = threadIdx.x; j < C; j += creal) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) f[k] += sf[k][j];
+      }
+      const bool dbl = MODE == 0 && colstats_cancels(f[0], f[1], n);
+      sums[threadIdx.x] = dbl ? f[NV - 2] : f[0];
+      sums[creal + threadIdx.x] = dbl ? f[NV - 1] : f[1];
     }
     return;
   }
-  if (ty == 0 && c < C) { sums[c] = tot[0]; sums[creal + c] = tot[1]; }
+  if (ty == 0 && c < C) {
+    const bool dbl = MODE == 0 && colstats_cancels(tot[0], tot[1], n);
+    sums[c] = dbl ? tot[NV - 2] : tot[0];
+    sums[creal + c] = dbl ? tot[NV - 1] : tot[1];
+  }
 }
 
 __global__ void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -509,10 +546,10 @@ static int colreduce_fold(int rows, int C) {
   while (C * k * 2 <= 64 && rows % (k * 2) == 0) k *= 2;
   return k;
 }
-// stripes: the workspace holds one partial (2 x 64 doubles) per workgroup; without a workspace one stripe per column block
-static int colreduce_grid_y(int rows, int gx, bool have_ws) {
+// stripes: the workspace holds one partial (nv x 64 doubles; 4 for the statistics, 2 for the backward sums) per workgroup; without a workspace one stripe per column block
+static int colreduce_grid_y(int rows, int gx, bool have_ws, int nv) {
   if (!have_ws) return 1;
-  const int cap = (int)(CTTS_WS_RED_P1_BYTES / (2 * 64 * sizeof(double))) / gx;
+  const int cap = (int)(CTTS_WS_RED_P1_BYTES / (nv * 64 * sizeof(double))) / gx;
   return max(1, min(min(max(1, 1024 / gx), rows / 64), min(cap, CTTS_RED_MAX_GROUPS * 64)));
 }
 
@@ -520,7 +557,7 @@ extern "C" int ctts_colstats(const float* x, double* sums, int rows, int C, void
   CTTS_REQUIRE(x && sums && rows > 0 && C > 0 && (C + 63) / 64 <= CTTS_RED_MAX_COLBLOCKS, "ctts_colstats: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   const int k = colreduce_fold(rows, C), Cv = C * k, Rv = rows / k, gx = (Cv + 63) / 64;
-  const int gy = colreduce_grid_y(Rv, gx, ws != nullptr);
+  const int gy = colreduce_grid_y(Rv, gx, ws != nullptr, 4);
   hipLaunchKernelGGL((colreduce_kernel<0>), dim3(gx, gy), dim3(256), 0, st, x, nullptr, nullptr,
                      nullptr, nullptr, nullptr, sums, Rv, Cv, C, 0, 0.f, nullptr, 0u, (unsigned char*)ws, ctts_red_group(gy));
   CTTS_CHECK_LAUNCH("ctts_colstats");
@@ -591,7 +628,7 @@ extern "C" int ctts_bn_bwd_reduce(const float* dy, const float* x, const float* 
                "ctts_bn_bwd_reduce: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   const int k = colreduce_fold(rows, C), Cv = C * k, Rv = rows / k, gx = (Cv + 63) / 64;
-  const int gy = colreduce_grid_y(Rv, gx, ws != nullptr);
+  const int gy = colreduce_grid_y(Rv, gx, ws != nullptr, 2);
   hipLaunchKernelGGL((colreduce_kernel<1>), dim3(gx, gy), dim3(256), 0, st, x, dy, mean, rstd,
                      gamma, beta, sums, Rv, Cv, C, act, p_drop, seed, drop_offset, (unsigned char*)ws, ctts_red_group(gy));
   CTTS_CHECK_LAUNCH("ctts_bn_bwd_reduce");
