@@ -7,7 +7,9 @@ operand is the activation itself with overlapping rows (row stride = C_in, K = k
 reference's transpose/contiguous copies (10.6 % of its CPU time)
 disappear and bias / scale / activation / dropout / residual / pad-mask fuse into the GEMM epilogue.
 """
+import contextlib
 import math
+import os as _os
 
 import torch
 
@@ -201,25 +203,18 @@ class _OnWgradStream:
         return self.ctx.__exit__(*exc)
 
 
-class _Inline:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
-
-
 def _wgrad_scope(fused, *operands, rows=None):
     if not fused or _WGRAD["stream"] is None:
-        return _Inline()
+        return contextlib.nullcontext()
     if _WGRAD["max_rows"] is not None and rows is not None and rows > _WGRAD["max_rows"]:
-        return _Inline()
+        return contextlib.nullcontext()
     return _OnWgradStream(*operands)
 
 
-import os as _os
+# tuning knob; 0 = never split the data-gradient reduction
 _DGRAD_SPLIT_K = int(_os.environ.get("CTTS_DGRAD_SPLIT_K", "1"))
-_FUSE_EPILOGUE_BWD = _os.environ.get("CTTS_FUSE_EPI_BWD", "1") != "0"      # EpiLink: producer's epilogue backward inside the consumer's dgrad GEMM     # tuning knob; 0 = never split the data-gradient reduction
+# EpiLink: producer's epilogue backward inside the consumer's dgrad GEMM
+_FUSE_EPILOGUE_BWD = _os.environ.get("CTTS_FUSE_EPI_BWD", "1") != "0"
 _WGRAD_SPLIT_MULT = float(_os.environ.get("CTTS_WGRAD_SPLIT_MULT", "1"))
 _WGRAD_SPLIT_CAP = int(_os.environ.get("CTTS_WGRAD_SPLIT_CAP", "512"))      # a split-K piece reduces over at least this many rows
 
@@ -263,6 +258,155 @@ class EpiLink:
         return (self.Z, self.act, self.p_drop, self.seed, self.drop_offset, self.gen, self.conv_dims)
 
 
+def _drop_args(p_drop, drop):
+    """(p_drop, seed, offset) of a dropout call site.  Offsets are assigned in program order: one is drawn from `drop` (a kernels.DropCtx)
+    exactly when the site really drops; otherwise the kernels get p_drop = 0 and no seed."""
+    if drop is None or not p_drop > 0:
+        return 0.0, None, 0
+    return p_drop, drop.seed, drop.next_offset()
+
+
+def _param_colsum(x2d, p, scale=1.0, fused=None):
+    """Gradient of a parameter that is a column sum (bias): scale * colsum(x2d), ADDED to the parameter's accumulation buffer when it has
+    one (-> None for autograd), else returned in the parameter's shape.  `fused`: the decision when it was taken earlier (_RelAttnSplit
+    decides in its forward and then adds into `p.grad`); None = decide now (_grad_of)."""
+    acc = _grad_of(p) if fused is None else (p.grad if fused else None)
+    if acc is not None:
+        K.colsum(x2d, scale=scale, acc_into=acc.view(-1))
+        return None
+    return K.colsum(x2d, scale=scale).view_as(p)
+
+
+def _matmul_wgrad(dY, x, w, **kw):
+    """Weight gradient dW [N, Kd] (+)= dY^T x of y = x w^T over all rows of x [..., Kd] / dY [..., N].  With an accumulation buffer for `w`
+    (_grad_of) the ordered split-K sum is ADDED to it - deferred to the stage's PartialSink unless a side stream runs the launch - and
+    autograd gets None; else it is WRITTEN into a fresh tensor (split_overwrite: no zero fill), which is returned.  `kw`: alpha, tile_map
+    and the ragged-row keywords of the launch."""
+    N, Kd = w.shape[0], x.shape[-1]
+    M = x.numel() // Kd
+    acc = _grad_of(w)
+    fused = acc is not None
+    dW = acc if fused else torch.empty_like(w)
+    with _wgrad_scope(fused, dY, x, rows=M):
+        K.gemm(dY, x, dW, N, Kd, M, N, Kd, Kd, False, False, split_k=max(2, _split_k_for(N, Kd, M)),
+               defer=fused and _WGRAD["stream"] is None, split_overwrite=not fused, **kw)
+    return None if fused else dW
+
+
+# ---- the stages of _LinearConv.backward -----------------------------------------------------------------------------------------
+# A launch is described ONCE, as (args, kw) = the positional and keyword arguments of K.gemm; the eligibility queries (K.gemm_takes_*)
+# are asked with that description and the launch is made with it.  Between the two only what the answer decides may change: real plane
+# sets for the placeholders, the tile schedule (which the plane kernels do not read), split_k when the persistent kernel declines.
+def _epilogue_bwd_stage(dY, Z, rowscale, seed, b, want_bias, has_res, delivered, act, alpha, p_drop, drop_offset):
+    """(dZ, d_res, dB): the gradient in front of the epilogue, of the residual operand and of the bias (None: not wanted, or added to
+    its accumulation buffer)."""
+    if delivered or (rowscale is None and act == ACT_NONE and p_drop == 0):
+        # delivered: the EpiLink consumer's data-gradient GEMM already applied this layer's epilogue backward, dY IS dZ;
+        # plain linear: nothing to undo.  Either way the bias gradient is alpha * colsum(dY)
+        dB = _param_colsum(dY.view(-1, dY.shape[-1]), b, alpha) if want_bias else None
+        return dY, (dY if has_res else None), dB
+    # one pass: gm = dY * rowscale (gradient of the residual), dZ = gm * drop * act'(Z), bias gradient = alpha * colsum(dZ)
+    acc = _grad_of(b) if want_bias else None
+    dZ, gm, dBn = K.epilogue_bwd(dY, rowscale, Z, act, p_drop, seed, drop_offset, want_gm=has_res and rowscale is not None,
+                                 want_bias=want_bias, bias_scale=alpha, bias_acc_into=acc)
+    d_res = (gm if rowscale is not None else dY) if has_res else None
+    return dZ, d_res, (dBn if (want_bias and acc is None) else None)
+
+
+def _conv_dgrad(dZ, w, x, dz_planes, pad, alpha, pr, rl):
+    """(dX, plane set of dZ or None) of the Conv1d whose forward view had `pad` zeros in front."""
+    N, Cin, ksize = w.shape
+    M, T, Kd = x.numel() // Cin, x.shape[-2], ksize * N
+    pad_d = ksize - 1 - pad              # data gradient: correlation with the flipped taps (equal to `pad` for SAME with odd k)
+    wd = _DGRAD_W.take(w, (Cin, Kd))          # prepared for the whole model at the start of the step (prepare_dgrad_weights)
+    if wd is None:
+        wd = torch.empty(Cin, Kd, dtype=torch.float32, device=x.device)
+        wmaj = _gemm_major(w)
+        K.conv_weight_repack(wmaj if wmaj is not None else w.contiguous(), wd, N, Cin, ksize, 4 if wmaj is not None else 1)
+    # few output tiles but a long reduction (FFN conv dgrad: 1024 tiles, K = 9216): split K so that the launch fills
+    # all 256 CUs x 8 resident workgroups (atomic accumulation into a zero-filled dX)
+    tiles = -(-M // 64) * -(-Cin // 64)
+    sk = min(4, max(2, -(-2304 // tiles))) if (_DGRAD_SPLIT_K and tiles < 1536 and Kd >= 4096) else 1
+    dX = torch.empty_like(x)             # split: the ordered reduce launch writes every element (zeros in padded tiles)
+    args = (dZ, wd, dX, M, Cin, Kd, N, Kd, Cin, True, True)
+    kw = dict(conv=(T, pad_d, N), alpha=alpha, row_halo=pad_d, split_k=1, split_overwrite=True, **rl)
+    planes = _operand_planes("dgrad", w, args, kw, a_given=dz_planes)
+    if planes:          # pre-split operands on the persistent plane kernel: balances the reduction itself, writes every element
+        K.gemm(*args, **kw, **planes)
+        return dX, planes["a_planes"]
+    kw["tile_map"] = pr.tile_map(pad_d, M) if pr is not None else None
+    # the persistent stream-K kernel balances the reduction itself: no split, no zero fill, no atomics
+    if sk > 1 and not K.gemm_takes_persistent(*args, **kw):
+        kw["split_k"] = sk
+    K.gemm(*args, **kw)
+    return dX, dz_planes
+
+
+def _conv_wgrad(dZ, x, w, dz_planes, x_planes, pad, alpha, kmap, rl):
+    """Weight gradient of the Conv1d as ONE GEMM dWf [Cout, k * Cin] (+)= dZ^T (*) x.  A fusable GEMM-major parameter gets the split-K
+    partials added straight into param.grad; otherwise dWf is a fresh matrix that is repacked into param.grad (fused), viewed with the
+    parameter's own strides (GEMM-major) or repacked into a new tensor.  -> dW for autograd (None when fused)."""
+    N, Cin, ksize = w.shape
+    M, T, Kd = x.numel() // Cin, x.shape[-2], ksize * Cin
+    acc = _grad_of(w)
+    fused = acc is not None
+    gmaj = _gemm_major(acc) if fused else None
+    dwf = gmaj if gmaj is not None else torch.empty(N, Kd, dtype=torch.float32, device=x.device)
+    args = (dZ, x, dwf, N, Kd, M, N, Cin, Kd, False, False)
+    kw = dict(conv=(T, pad, Cin), conv_on_b=True, split_k=max(2, _split_k_for(N, Kd, M)), alpha=alpha, tile_map=kmap,
+              split_overwrite=gmaj is None, **rl)
+    wp = _wgrad_planes(args, kw, dz_planes, x_planes, Cin)
+    # the side stream reads dZ, x, the plane sets and a fresh dwf until the join
+    with _wgrad_scope(fused, dZ, x, dwf, *wp.values(), rows=M):
+        K.gemm(*args, defer=gmaj is not None and _WGRAD["stream"] is None, **kw, **wp)
+        if gmaj is not None:
+            return None
+        if fused:
+            K.conv_weight_repack(dwf, acc, N, Cin, ksize, 3)
+            return None
+        if _gemm_major(w) is not None:
+            return dwf.view(N, ksize, Cin).permute(0, 2, 1)      # a view with the parameter's own strides: no repack
+        return K.conv_weight_repack(dwf, torch.empty_like(w), N, Cin, ksize, 2)
+
+
+def _matmul_dgrad(dZ, w, x, alpha, pr, rl, link_snap=None):
+    """dX = alpha * dZ w.  `link_snap` (EpiLink consumer): the producer's epilogue as it was at this layer's forward - its backward,
+    mask / (1-p) * act'(Z_producer), is applied in this GEMM's epilogue, so dX is the PRODUCER's dZ."""
+    N, Cin = w.shape[0], x.shape[-1]
+    M = x.numel() // Cin
+    dX = torch.empty_like(x)
+    args = (dZ, w, dX, M, Cin, N, N, Cin, Cin, True, False)
+    kw = dict(alpha=alpha, tile_map=pr.tile_map(0, M) if pr is not None else None, **rl)
+    if link_snap is None:
+        K.gemm(*args, **kw)
+        return dX
+    lZ, lact, lp, lseed, loff, _, lconv = link_snap
+    kw.update(epi_bwd=True, Z=lZ, ldz=Cin, act=lact, p_drop=lp, seed=lseed, drop_offset=loff)
+    # dX IS the producer convolution's dZ: when that layer's data gradient runs on the plane kernel and this launch runs on the
+    # weight-stationary kernel (the only one whose epilogue writes planes), dZ arrives with its operand planes - no ctts_split_planes
+    # pass over the [M, 4C] gradient (round 6)
+    cpl = None
+    if lconv is not None and K.PRODUCER_PLANES and dZ.is_cuda and Cin % 32 == 0 and K.plane_shape_ok(M, lconv[0], lconv[1] * Cin, Cin):
+        cand = K.new_planes(M, Cin, dZ.device)
+        if K.gemm_takes_weight_stationary(*args, c_planes=cand, **kw):
+            cpl = cand
+    K.gemm(*args, c_planes=cpl, **kw)
+    if cpl is not None:
+        K.attach_planes(dX, cpl)
+    return dX
+
+
+def _linear_wgrad(dZ, x, w, alpha, kmap, rl):
+    """weight gradient of the plain matmul layer (None when it was added to the parameter's accumulation buffer)"""
+    N, Cin = w.shape[0], x.shape[-1]
+    if N == 1 and rl.get("row_lens") is None:
+        # one-output head: dW[0,:] = alpha * sum_r dZ[r] x[r,:] - a weighted column sum, not a 1 x C GEMM
+        acc = _grad_of(w)
+        got = K.weighted_colsum(x.view(-1, Cin), dZ.reshape(-1), scale=alpha, acc_into=acc.view(-1) if acc is not None else None)
+        return None if acc is not None else got.view(1, Cin)
+    return _matmul_wgrad(dZ, x, w, alpha=alpha, tile_map=kmap, **rl)
+
+
 class _LinearConv(torch.autograd.Function):
     """y = rowscale * (residual + drop(act(alpha * (x (*) w + b))))      (*) = matmul or Conv1d('same')
 
@@ -270,42 +414,36 @@ class _LinearConv(torch.autograd.Function):
     modules.py:140-148,1299-1356 and CompTransTTS.py:133 (fwd, dgrad, wgrad all on MFMA)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, residual, rowscale, act, alpha, p_drop, seed, drop_offset, ksize, row_lens, row_T, pr=None, link=None,
-                link_role=0, pad_left=None):
+    def forward(ctx, x, w, b, residual, rowscale, act, alpha, p_drop, seed, drop_offset, ksize=0, pad_left=0, pr=None, link=None,
+                link_role=0):
+        """ksize: 0 = matmul, else the Conv1d kernel size with `pad_left` zeros in front of the sequence ((k-1)//2 = nn.Conv1d(padding=
+        k//2) "SAME"; k-1 = ConstantPad1d((k-1, 0)) "LEFT", causal); pr: the PadRows of the (b, t) rows or None"""
         x = x.contiguous()
         Cin = x.shape[-1]
         M = x.numel() // Cin
         N = w.shape[0]
         out = torch.empty(*x.shape[:-1], N, dtype=torch.float32, device=x.device)
         Z = torch.empty_like(out) if act != ACT_NONE else None
-        if ksize:
-            T = x.shape[-2]
-            wf = _gemm_major(w)
-            if wf is None:
-                wf = torch.empty(N, ksize * Cin, dtype=torch.float32, device=x.device)
-                K.conv_weight_repack(w.contiguous(), wf, N, Cin, ksize, 0)
-            # zeros in front of the sequence: (k-1)//2 = nn.Conv1d(padding=k//2) "SAME"; k-1 = ConstantPad1d((k-1, 0)) "LEFT" (causal)
-            ctx.pad_left = (ksize - 1) // 2 if pad_left is None else int(pad_left)
-            conv = (T, ctx.pad_left, Cin)
-            Kdim = ksize * Cin
-        else:
-            wf, conv, Kdim = w.contiguous(), None, Cin
+        wf, conv, Kdim = (_gemm_major(w), (x.shape[-2], int(pad_left), Cin), ksize * Cin) if ksize else (w.contiguous(), None, Cin)
+        if wf is None:
+            wf = K.conv_weight_repack(w.contiguous(), torch.empty(N, Kdim, dtype=torch.float32, device=x.device), N, Cin, ksize, 0)
         if residual is not None:
             residual = residual.contiguous()
-        gk = dict(conv=conv, alpha=alpha, bias=b, Z=Z, ldz=N, act=act, p_drop=p_drop, seed=seed, drop_offset=drop_offset, R=residual, ldr=N,
+        row_lens, row_T = (pr.lens, pr.T) if pr is not None else (None, 0)
+        args = (x, wf, out, M, N, Kdim, Cin, Kdim, N, True, True)
+        kw = dict(conv=conv, alpha=alpha, bias=b, Z=Z, ldz=N, act=act, p_drop=p_drop, seed=seed, drop_offset=drop_offset, R=residual, ldr=N,
                   rowscale=rowscale, row_lens=row_lens, row_T=row_T, row_halo=0)
         # reference train.py:59,104 `with amp.autocast(args.use_amp)`: honoured by the launches the plane kernels take (the Conv1d layers
         # with many rows) - operands rounded to bf16, one MFMA term, fp32 accumulate and fp32 tensors everywhere; the backward of the
         # layer uses the arithmetic its forward ran with.  Everything else stays fp32-class.  Reduced precision: opt-in, own tolerance.
         ctx.amp = (K.amp_split() if (ksize and x.is_cuda and torch.is_autocast_enabled("cuda")) else None)
         if ctx.amp is not None:
-            gk["bf16_split"] = ctx.amp
-        planes = _operand_planes("fwd", w, x.view(M, Cin), wf, M, N, Kdim, Cin, Kdim, N, out, gk, a_given=K.planes_of(x)) if ksize else {}
-        K.gemm(x, wf, out, M, N, Kdim, Cin, Kdim, N, True, True, tile_map=pr.tile_map(0, M) if (pr is not None and not planes) else None,
-               **gk, **planes)
+            kw["bf16_split"] = ctx.amp
+        planes = _operand_planes("fwd", w, args, kw, a_given=K.planes_of(x)) if ksize else {}
+        K.gemm(*args, tile_map=pr.tile_map(0, M) if (pr is not None and not planes) else None, **kw, **planes)
         ctx.x_planes = planes.get("a_planes")        # the weight-gradient launch reads the same plane set (gemm_plw.hip)
         ctx.save_for_backward(x, w, Z, rowscale, seed, row_lens, b)
-        ctx.cfg = (act, alpha, p_drop, drop_offset, ksize, b is not None, residual is not None, row_T)
+        ctx.cfg = (act, alpha, p_drop, drop_offset, ksize, int(pad_left), residual is not None)
         ctx.pr = pr
         ctx.link, ctx.link_role, ctx.link_snap = None, 0, None
         if link is not None and _FUSE_EPILOGUE_BWD:
@@ -319,134 +457,34 @@ class _LinearConv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dY):
         x, w, Z, rowscale, seed, row_lens, b = ctx.saved_tensors
-        act, alpha, p_drop, drop_offset, ksize, has_bias, has_res, row_T = ctx.cfg
-        rl = dict(row_lens=row_lens, row_T=row_T) if row_lens is not None else {}
-        if getattr(ctx, "amp", None) is not None:
-            rl["bf16_split"] = ctx.amp           # travels with every GEMM of this backward (only the plane kernels act on it)
+        act, alpha, p_drop, drop_offset, ksize, pad, has_res = ctx.cfg
         pr = ctx.pr
+        want_x, want_w, want_b = ctx.needs_input_grad[:3]
+        rl = dict(row_lens=row_lens, row_T=pr.T) if row_lens is not None else {}
+        if ctx.amp is not None:
+            rl["bf16_split"] = ctx.amp           # travels with every GEMM of this backward (only the plane kernels act on it)
         # weight gradients reduce over the (b,t) rows: the same device-built map, read as a schedule of the active 64-row K-blocks
-        kmap = pr.tile_map(0, x.numel() // x.shape[-1]) if (pr is not None and row_lens is not None) else None
-        dY = dY.contiguous()
-        Cin = x.shape[-1]
-        M = x.numel() // Cin
-        N = w.shape[0]
-        dX = dW = dB = None
-        want_bias = has_bias and ctx.needs_input_grad[2]
-        fuse_bias = want_bias and _fusable(b)
-        if ctx.link_role == 1 and ctx.link_gen in ctx.link.done:
-            # the consumer's data-gradient GEMM already applied this layer's epilogue backward: dY IS dZ (EpiLink)
+        kmap = pr.tile_map(0, x.numel() // x.shape[-1]) if row_lens is not None else None
+        delivered = ctx.link_role == 1 and ctx.link_gen in ctx.link.done        # EpiLink: the consumer handed this producer its dZ
+        if delivered:
             ctx.link.done.discard(ctx.link_gen)
-            dZ, d_res = dY, None
-            if want_bias:
-                if fuse_bias:
-                    K.colsum(dZ.view(M, N), scale=alpha, acc_into=_grad_of(b))
-                else:
-                    dB = K.colsum(dZ.view(M, N), scale=alpha)
-        elif rowscale is None and act == ACT_NONE and p_drop == 0:
-            dZ, d_res = dY, (dY if has_res else None)          # plain linear: nothing to undo
-            if want_bias:
-                if fuse_bias:
-                    K.colsum(dZ.view(M, N), scale=alpha, acc_into=_grad_of(b))
-                else:
-                    dB = K.colsum(dZ.view(M, N), scale=alpha)
-        else:
-            # one pass: gm = dY * rowscale (gradient of the residual), dZ = gm * drop * act'(Z), bias gradient = alpha * colsum(dZ)
-            dZ, gm, dBn = K.epilogue_bwd(dY, rowscale, Z, act, p_drop, seed, drop_offset, want_gm=has_res and rowscale is not None,
-                                         want_bias=want_bias, bias_scale=alpha, bias_acc_into=_grad_of(b) if fuse_bias else None)
-            d_res = (gm if rowscale is not None else dY) if has_res else None
-            if want_bias and not fuse_bias:
-                dB = dBn
-        dz_planes = K.planes_of(dZ) if ksize else None          # written by dZ's producer (BatchNorm backward, the EpiLink GEMM epilogue)
+        dZ, d_res, dB = _epilogue_bwd_stage(dY.contiguous(), Z, rowscale, seed, b, b is not None and want_b, has_res, delivered,
+                                            act, alpha, p_drop, drop_offset)
+        dX = dW = None
         if ksize:
-            T = x.shape[-2]
-            pad = ctx.pad_left                   # forward / weight-gradient view
-            pad_d = ksize - 1 - pad              # data gradient: correlation with the flipped taps (equal to `pad` for SAME with odd k)
-            if ctx.needs_input_grad[0]:
-                wd = _DGRAD_W.take(w, (Cin, ksize * N))          # prepared for the whole model at the start of the step (prepare_dgrad_weights)
-                if wd is None:
-                    wd = torch.empty(Cin, ksize * N, dtype=torch.float32, device=x.device)
-                    wmaj = _gemm_major(w)
-                    if wmaj is not None:
-                        K.conv_weight_repack(wmaj, wd, N, Cin, ksize, 4)
-                    else:
-                        K.conv_weight_repack(w.contiguous(), wd, N, Cin, ksize, 1)
-                # few output tiles but a long reduction (FFN conv dgrad: 1024 tiles, K = 9216): split K so that the launch fills
-                # all 256 CUs x 8 resident workgroups (atomic accumulation into a zero-filled dX)
-                tiles = -(-M // 64) * -(-Cin // 64)
-                sk = min(4, max(2, -(-2304 // tiles))) if (_DGRAD_SPLIT_K and tiles < 1536 and ksize * N >= 4096) else 1
-                dX = torch.empty_like(x)             # split: the ordered reduce launch writes every element (zeros in padded tiles)
-                dg0 = dict(conv=(T, pad_d, N), alpha=alpha, row_halo=pad_d, **rl)
-                planes = _operand_planes("dgrad", w, dZ.view(M, N), wd, M, Cin, ksize * N, N, ksize * N, Cin, dX, dict(split_overwrite=True, **dg0),
-                                         a_given=dz_planes)
-                if planes:          # pre-split operands on the persistent plane kernel: balances the reduction itself, writes every element
-                    dz_planes = planes["a_planes"]
-                    K.gemm(dZ, wd, dX, M, Cin, ksize * N, N, ksize * N, Cin, True, True, split_k=1, split_overwrite=True, **dg0, **planes)
-                else:
-                    dg = dict(tile_map=pr.tile_map(pad_d, M) if pr is not None else None, **dg0)
-                    if sk > 1 and K.gemm_takes_persistent(dZ, wd, x, M, Cin, ksize * N, N, ksize * N, Cin, True, True, split_k=1, **dg):
-                        sk = 1          # the persistent stream-K kernel balances the reduction itself: no split, no zero fill, no atomics
-                    K.gemm(dZ, wd, dX, M, Cin, ksize * N, N, ksize * N, Cin, True, True, split_k=sk, split_overwrite=True, **dg)
-            if ctx.needs_input_grad[1]:
-                Kd = ksize * Cin
-                fused = _fusable(w)
-                gmaj = _gemm_major(_grad_of(w)) if fused else None
-                wk = dict(conv=(T, pad, Cin), conv_on_b=True, split_k=max(2, _split_k_for(N, Kd, M)), alpha=alpha, **rl)
-                if gmaj is not None:             # GEMM-major parameter: the split-K partials are added straight into param.grad
-                    wp = _wgrad_planes(dZ.view(M, N), x.view(M, Cin), dz_planes, getattr(ctx, "x_planes", None), gmaj, N, Kd, M, Cin, wk)
-                    with _wgrad_scope(True, dZ, x, *wp.values(), rows=M):        # the plane sets too: read on the side stream until the join
-                        K.gemm(dZ, x, gmaj, N, Kd, M, N, Cin, Kd, False, False, tile_map=kmap, defer=_WGRAD["stream"] is None, **wk, **wp)
-                else:
-                    dwf = torch.empty(N, Kd, dtype=torch.float32, device=x.device)
-                    wk["split_overwrite"] = True
-                    wp = _wgrad_planes(dZ.view(M, N), x.view(M, Cin), dz_planes, getattr(ctx, "x_planes", None), dwf, N, Kd, M, Cin, wk)
-                    with _wgrad_scope(fused, dZ, x, dwf, *wp.values(), rows=M):
-                        K.gemm(dZ, x, dwf, N, Kd, M, N, Cin, Kd, False, False, tile_map=kmap, **wk, **wp)
-                        if fused:
-                            K.conv_weight_repack(dwf, _grad_of(w), N, Cin, ksize, 3)
-                        elif _gemm_major(w) is not None:
-                            dW = dwf.view(N, ksize, Cin).permute(0, 2, 1)      # a view with the parameter's own strides: no repack
-                        else:
-                            dW = torch.empty_like(w)
-                            K.conv_weight_repack(dwf, dW, N, Cin, ksize, 2)
+            dz_planes = K.planes_of(dZ)          # written by dZ's producer (BatchNorm backward, the EpiLink GEMM epilogue)
+            if want_x:
+                dX, dz_planes = _conv_dgrad(dZ, w, x, dz_planes, pad, alpha, pr, rl)
+            if want_w:
+                dW = _conv_wgrad(dZ, x, w, dz_planes, ctx.x_planes, pad, alpha, kmap, rl)
         else:
-            if ctx.needs_input_grad[0]:
-                dX = torch.empty_like(x)
-                if ctx.link_role == 2:   # hand the producer its dZ: mask / (1-p) * act'(Z_producer) applied in this GEMM's epilogue
-                    lZ, lact, lp, lseed, loff, lgen, lconv = ctx.link_snap     # the producer's epilogue as it was at THIS forward
-                    gk = dict(alpha=alpha, epi_bwd=True, Z=lZ, ldz=Cin, act=lact, p_drop=lp, seed=lseed, drop_offset=loff,
-                              tile_map=pr.tile_map(0, M) if pr is not None else None, **rl)
-                    # dX IS the producer convolution's dZ: when that layer's data gradient runs on the plane kernel and this launch runs on
-                    # the weight-stationary kernel (the only one whose epilogue writes planes), dZ arrives with its operand planes - no
-                    # ctts_split_planes pass over the [M, 4C] gradient (round 6)
-                    cpl = None
-                    if (lconv is not None and K.PRODUCER_PLANES and dZ.is_cuda and Cin % 32 == 0
-                            and K.plane_shape_ok(M, lconv[0], lconv[1] * Cin, Cin)):
-                        cand = K.new_planes(M, Cin, dZ.device)
-                        if K.gemm_takes_weight_stationary(dZ, w, dX, M, Cin, N, N, Cin, Cin, True, False, c_planes=cand, **gk):
-                            cpl = cand
-                    K.gemm(dZ, w, dX, M, Cin, N, N, Cin, Cin, True, False, c_planes=cpl, **gk)
-                    if cpl is not None:
-                        K.attach_planes(dX, cpl)
-                    ctx.link.done.add(lgen)
-                else:
-                    K.gemm(dZ, w, dX, M, Cin, N, N, Cin, Cin, True, False, alpha=alpha,
-                           tile_map=pr.tile_map(0, M) if pr is not None else None, **rl)
-            if ctx.needs_input_grad[1] and N == 1 and row_lens is None:
-                # one-output head: dW[0,:] = alpha * sum_r dZ[r] x[r,:] - a weighted column sum, not a 1 x C GEMM
-                fused = _fusable(w)
-                got = K.weighted_colsum(x.view(M, Cin), dZ.reshape(M), scale=alpha, acc_into=_grad_of(w).view(-1) if fused else None)
-                dW = None if fused else got.view(1, Cin)
-            elif ctx.needs_input_grad[1]:
-                fused = _fusable(w)
-                # fused: the ordered split-K sum is ADDED to param.grad (deferred to the stage's PartialSink); else it is WRITTEN into a fresh
-                # tensor (split_overwrite: no zero fill)
-                dW = _grad_of(w) if fused else torch.empty_like(w)
-                with _wgrad_scope(fused, dZ, x, rows=M):
-                    K.gemm(dZ, x, dW, N, Cin, M, N, Cin, Cin, False, False, split_k=max(2, _split_k_for(N, Cin, M)), alpha=alpha,
-                           tile_map=kmap, defer=fused and _WGRAD["stream"] is None, split_overwrite=not fused, **rl)
-                if fused:
-                    dW = None
-        return dX, dW, dB, d_res, None, None, None, None, None, None, None, None, None, None, None, None, None
+            if want_x:
+                dX = _matmul_dgrad(dZ, w, x, alpha, pr, rl, ctx.link_snap if ctx.link_role == 2 else None)
+                if ctx.link_role == 2:
+                    ctx.link.done.add(ctx.link_snap[5])
+            if want_w:
+                dW = _linear_wgrad(dZ, x, w, alpha, kmap, rl)
+        return (dX, dW, dB, d_res) + (None,) * (len(ctx.needs_input_grad) - 4)
 
 
 # data-gradient operands of the Conv1d weights, keyed by the weight's device address; filled by prepare_dgrad_weights at the start of a
@@ -480,16 +518,19 @@ _DGRAD_W = _DgradCache()
 _PLANES = {"fwd": {}, "dgrad": {}, "want_fwd": set(), "want_dgrad": set()}
 
 
-def _operand_planes(kind, w, a_mat, b_mat, M, N, Kdim, lda, ldb, ldc, out, gk, a_given=None):
-    """{} or dict(a_planes=, b_planes=) for K.gemm: the three-way bf16 split of the activation-side matrix `a_mat` [M, lda] (made here:
-    one streaming launch) and of the weight-side matrix `b_mat` [N, Kdim] (from the step's cache) - when the library would run this
-    launch on the plane kernel (asked with placeholder planes: no device work)."""
-    conv = gk.get("conv")
+def _operand_planes(kind, w, args, kw, a_given=None):
+    """{} or dict(a_planes=, b_planes=) for the launch K.gemm(*args, **kw) of a Conv1d forward ("fwd") or data gradient ("dgrad"): the
+    three-way bf16 split of the activation-side matrix A [M, lda] (made here: one streaming launch) and of the weight-side matrix
+    B [N, Kdim] of the weight `w` (from the step's cache) - when the library would run this launch on the plane kernel (asked with
+    placeholder planes: no device work)."""
+    A, b_mat, _, M, N, Kdim, lda = args[:7]
+    conv = kw.get("conv")
     if not K.plane_shape_ok(M, N, Kdim, conv[2] if conv is not None else None):
         return {}
-    if not (a_mat.is_contiguous() and b_mat.is_contiguous() and a_mat.shape[1] % 32 == 0 and b_mat.shape[1] % 32 == 0):
+    a_mat = A.view(M, lda)
+    if not (a_mat.is_contiguous() and b_mat.is_contiguous() and lda % 32 == 0 and b_mat.shape[1] % 32 == 0):
         return {}
-    if not K.gemm_takes_planes(a_mat, b_mat, out, M, N, Kdim, lda, ldb, ldc, True, True, a_planes=_FakePlanes(a_mat), b_planes=_FakePlanes(b_mat), **gk):
+    if not K.gemm_takes_planes(*args, a_planes=_FakePlanes(a_mat), b_planes=_FakePlanes(b_mat), **kw):
         return {}
     ent = _PLANES[kind].get(w.data_ptr())
     if ent is not None and ent[1] == _wstamp(w) and ent[0].numel() == 3 * b_mat.numel():
@@ -501,15 +542,17 @@ def _operand_planes(kind, w, a_mat, b_mat, M, N, Kdim, lda, ldb, ldc, out, gk, a
     return dict(a_planes=a_given if a_given is not None else K.split_planes([a_mat])[0], b_planes=bp)
 
 
-def _wgrad_planes(dz_mat, x_mat, dz_pl, x_pl, out, Mo, No, Kred, cin, kw):
-    """{} or dict(a_planes=, b_planes=) for the weight-gradient launch `out [Mo, No] (+)= dz_mat^T (*) x_mat`: the ROW-MAJOR plane sets of
-    dZ (made for the data-gradient launch) and of x (made for the forward launch) are what csrc/gemm_plw.hip reads - it transposes in
-    the LDS; a set that is not at hand (first layer: no data gradient; forward on another kernel) is split here."""
-    if not K.plane_wgrad_shape_ok(Mo, No, Kred, cin) or not (dz_mat.is_contiguous() and x_mat.is_contiguous()):
+def _wgrad_planes(args, kw, dz_pl, x_pl, cin):
+    """{} or dict(a_planes=, b_planes=) for the weight-gradient launch K.gemm(*args, **kw), `out [Mo, No] (+)= dZ^T (*) x`: the ROW-MAJOR
+    plane sets of dZ (made for the data-gradient launch) and of x (made for the forward launch) are what csrc/gemm_plw.hip reads - it
+    transposes in the LDS; a set that is not at hand (first layer: no data gradient; forward on another kernel) is split here."""
+    dZ, x, _, Mo, No, Kred = args[:6]
+    if not K.plane_wgrad_shape_ok(Mo, No, Kred, cin) or not (dZ.is_contiguous() and x.is_contiguous()):
         return {}
+    dz_mat, x_mat = dZ.view(Kred, Mo), x.view(Kred, cin)
     a = dz_pl if dz_pl is not None else _FakePlanes(dz_mat)
     b = x_pl if x_pl is not None else _FakePlanes(x_mat)
-    if not K.gemm_takes_planes(dz_mat, x_mat, out, Mo, No, Kred, Mo, cin, No, False, False, a_planes=a, b_planes=b, **kw):
+    if not K.gemm_takes_planes(*args, a_planes=a, b_planes=b, **kw):
         return {}
     made = iter(K.split_planes([m for m, pl in ((dz_mat, dz_pl), (x_mat, x_pl)) if pl is None]))
     return dict(a_planes=dz_pl if dz_pl is not None else next(made), b_planes=x_pl if x_pl is not None else next(made))
@@ -575,21 +618,18 @@ class PadRows:
 
 
 def _pad_rows(pad_rows):
-    if pad_rows is None:
-        return None, 0, None
-    if isinstance(pad_rows, PadRows):
-        return pad_rows.lens, pad_rows.T, pad_rows
-    return pad_rows[0], int(pad_rows[1]), PadRows(pad_rows[0], pad_rows[1])
+    """the PadRows of `pad_rows` = None, a PadRows or (lens, T)"""
+    if pad_rows is None or isinstance(pad_rows, PadRows):
+        return pad_rows
+    return PadRows(pad_rows[0], pad_rows[1])
 
 
 def linear(x, w, b=None, act=ACT_NONE, alpha=1.0, residual=None, rowscale=None, p_drop=0.0, drop=None, pad_rows=None, link=None,
            link_role=0):
     """pad_rows=(lens int32 [B], T) or an ops.PadRows: rows (b,t) with t >= lens[b] are padding - their outputs are don't-care
     (written as zero) and the incoming gradient there is zero, so whole padded tiles / K-blocks are skipped."""
-    seed, off = (drop.seed, drop.next_offset()) if (drop is not None and p_drop > 0) else (None, 0)
-    rl, rT, pr = _pad_rows(pad_rows)
-    return _LinearConv.apply(x, w, b, residual, rowscale, act, alpha, p_drop if seed is not None else 0.0, seed, off, 0, rl, rT, pr,
-                             link, link_role)
+    p_drop, seed, off = _drop_args(p_drop, drop)
+    return _LinearConv.apply(x, w, b, residual, rowscale, act, alpha, p_drop, seed, off, 0, 0, _pad_rows(pad_rows), link, link_role)
 
 
 def conv1d(x, w, b=None, act=ACT_NONE, alpha=1.0, residual=None, rowscale=None, p_drop=0.0, drop=None, pad_rows=None, link=None,
@@ -597,13 +637,12 @@ def conv1d(x, w, b=None, act=ACT_NONE, alpha=1.0, residual=None, rowscale=None, 
     """x [B,T,Cin], w [Cout,Cin,k] (nn.Conv1d layout), stride 1, output length T.  padding "SAME": k//2 zeros on both sides
     (nn.Conv1d(padding=k//2), odd k); "LEFT": k-1 zeros in front, none behind (ConstantPad1d((k-1, 0)): the reference's causal
     ffn_padding, transformer_fs2.py:209-218, modules.py:1328-1331)."""
-    seed, off = (drop.seed, drop.next_offset()) if (drop is not None and p_drop > 0) else (None, 0)
-    rl, rT, pr = _pad_rows(pad_rows)
+    p_drop, seed, off = _drop_args(p_drop, drop)
     if padding not in ("SAME", "LEFT"):
         raise ValueError(f"conv1d: padding '{padding}' (SAME or LEFT)")
     k = w.shape[2]
-    return _LinearConv.apply(x, w, b, residual, rowscale, act, alpha, p_drop if seed is not None else 0.0, seed, off,
-                             k, rl, rT, pr, link, link_role, (k - 1) if padding == "LEFT" else (k - 1) // 2)
+    pad_left = (k - 1) if padding == "LEFT" else (k - 1) // 2
+    return _LinearConv.apply(x, w, b, residual, rowscale, act, alpha, p_drop, seed, off, k, pad_left, _pad_rows(pad_rows), link, link_role)
 
 
 def _adjacent(ts):
@@ -654,14 +693,11 @@ class _PackedLinear(torch.autograd.Function):
             dX = torch.empty_like(x)
             K.gemm(dY, W, dX, M, Kd, N, N, Kd, Kd, True, False)
         gs = [_grad_of(w) for w in ws]
-        sk = max(2, _split_k_for(N, Kd, M))
         if all(g is not None for g in gs) and _adjacent(gs):
             G = torch.as_strided(gs[0], (N, Kd), (Kd, 1))
-            K.gemm(dY, x, G, N, Kd, M, N, Kd, Kd, False, False, split_k=sk, defer=_WGRAD["stream"] is None)
+            K.gemm(dY, x, G, N, Kd, M, N, Kd, Kd, False, False, split_k=max(2, _split_k_for(N, Kd, M)), defer=_WGRAD["stream"] is None)
             return (dX,) + (None,) * len(ws)
-        dW = torch.empty(N, Kd, dtype=torch.float32, device=x.device)
-        K.gemm(dY, x, dW, N, Kd, M, N, Kd, Kd, False, False, split_k=sk, split_overwrite=True)
-        return (dX,) + tuple(dW.split(ctx.sizes, 0))
+        return (dX,) + tuple(_matmul_wgrad(dY, x, W).split(ctx.sizes, 0))      # W is detached: always a fresh tensor
 
 
 def linear_packed(x, weights):
@@ -731,8 +767,8 @@ def layer_norm_res(x, gamma, beta, eps, planes_for=None):
 
 def layer_norm(x, gamma, beta, eps, rowscale=None, p_drop=0.0, drop=None):
     """y = rowscale * drop(LayerNorm(x)) over the last dim."""
-    seed, off = (drop.seed, drop.next_offset()) if (drop is not None and p_drop > 0) else (None, 0)
-    return _LayerNorm.apply(x, gamma, beta, eps, rowscale, p_drop if seed is not None else 0.0, seed, off)
+    p_drop, seed, off = _drop_args(p_drop, drop)
+    return _LayerNorm.apply(x, gamma, beta, eps, rowscale, p_drop, seed, off)
 
 
 # tuning knob; 1 = off (default since round 4: with the ordered reduce launch a 2-way split of the [T, T] x [T, dh] products costs more
@@ -935,8 +971,8 @@ def batch_norm_act(x, gamma, beta, running_mean, running_var, num_batches_tracke
     else:
         mean = running_mean
         rstd = torch.rsqrt(running_var + eps)
-    seed, off = (drop.seed, drop.next_offset()) if (drop is not None and p_drop > 0) else (None, 0)
-    return _BatchNormAct.apply(x, gamma, beta, mean, rstd, act, p_drop if seed is not None else 0.0, seed, off, bool(training),
+    p_drop, seed, off = _drop_args(p_drop, drop)
+    return _BatchNormAct.apply(x, gamma, beta, mean, rstd, act, p_drop, seed, off, bool(training),
                                bool(planes), bool(dx_planes))
 
 
@@ -1008,16 +1044,16 @@ class _PosEmbedAdd(torch.autograd.Function):
 def posembed_add(x, pos, table, alpha=None, rowscale=None, p_drop=0.0, drop=None):
     """rowscale * dropout(x + alpha * table[pos]): the fs2 `x + pos_embed_alpha * embed_positions(x)` (+ F.dropout + non-pad mask) fused;
     pos int32 [B, T] (kernels.positions), table [n_pos, C] (ops.sinusoid_table), alpha: the [1] parameter or None (= 1)."""
-    seed, off = (drop.seed, drop.next_offset()) if (drop is not None and p_drop > 0) else (None, 0)
-    return _PosEmbedAdd.apply(x, alpha, pos, table, rowscale, p_drop if seed is not None else 0.0, seed, off)
+    p_drop, seed, off = _drop_args(p_drop, drop)
+    return _PosEmbedAdd.apply(x, alpha, pos, table, rowscale, p_drop, seed, off)
 
 
 def rowscale_dropout(x, rowscale=None, p_drop=0.0, drop=None):
     """y = rowscale[row] * dropout(x)  (F.dropout followed by the non-pad mask multiply)."""
-    seed, off = (drop.seed, drop.next_offset()) if (drop is not None and p_drop > 0) else (None, 0)
+    p_drop, seed, off = _drop_args(p_drop, drop)
     if rowscale is None and seed is None:
         return x
-    return _RowscaleDropout.apply(x, rowscale, p_drop if seed is not None else 0.0, seed, off)
+    return _RowscaleDropout.apply(x, rowscale, p_drop, seed, off)
 
 
 class _GradScale(torch.autograd.Function):
@@ -1181,17 +1217,8 @@ class _RelAttnSplit(torch.autograd.Function):
         dqu, dqv, dkv = dqu.contiguous(), dqv.contiguous(), dkv.contiguous()
         Cc = dqu.shape[-1]
         u_bias, v_bias = ctx.biases
-        du = dv = None
-        if ctx.needs_input_grad[1]:
-            if ctx.fuse[0]:
-                K.colsum(dqu.view(-1, Cc), acc_into=u_bias.grad.view(-1))
-            else:
-                du = K.colsum(dqu.view(-1, Cc)).view_as(u_bias)
-        if ctx.needs_input_grad[2]:
-            if ctx.fuse[1]:
-                K.colsum(dqv.view(-1, Cc), acc_into=v_bias.grad.view(-1))
-            else:
-                dv = K.colsum(dqv.view(-1, Cc)).view_as(v_bias)
+        du = _param_colsum(dqu.view(-1, Cc), u_bias, fused=ctx.fuse[0]) if ctx.needs_input_grad[1] else None
+        dv = _param_colsum(dqv.view(-1, Cc), v_bias, fused=ctx.fuse[1]) if ctx.needs_input_grad[2] else None
         return K.relattn_split_bwd(dqu, dqv, dkv), du, dv
 
 
@@ -1200,9 +1227,9 @@ def relattn_split(qkv, u_bias, v_bias):
 
 
 def relpos_attention(qu, qv, kv, pos, n_heads, scale, p_drop=0.0, drop=None):
-    seed, off = (drop.seed, drop.next_offset()) if (drop is not None and p_drop > 0) else (None, 0)
+    p_drop, seed, off = _drop_args(p_drop, drop)
     fn = _FusedRelPosAttention if (_FUSED_ATTN is not False and K.mha_supported(qu.shape[-1], n_heads)) else _RelPosAttention
-    return fn.apply(qu, qv, kv, pos, n_heads, scale, p_drop if seed is not None else 0.0, seed, off)
+    return fn.apply(qu, qv, kv, pos, n_heads, scale, p_drop, seed, off)
 
 
 # ------------------------------------------------------------------------- unsupervised alignment operators
@@ -1732,26 +1759,10 @@ def _ff_dgrad(dY, w, R=None):
     return dX
 
 
-def _ff_wgrad(dY, x, w, b, want_w, want_b):
-    """weight / bias gradient of y = x w^T + b; accumulated straight into param.grad under gradient-accumulation fusion (a tied weight
-    then collects every layer's contribution in place), else returned"""
-    M, N = dY.shape
-    Kd = x.shape[1]
-    dW = dB = None
-    if want_w:
-        fused = _fusable(w)
-        dW = _grad_of(w) if fused else torch.empty_like(w)
-        with _wgrad_scope(fused, dY, x, rows=M):
-            K.gemm(dY, x, dW, N, Kd, M, N, Kd, Kd, False, False, split_k=max(2, _split_k_for(N, Kd, M)),
-                   defer=fused and _WGRAD["stream"] is None, split_overwrite=not fused)
-        if fused:
-            dW = None
-    if want_b:
-        if _fusable(b):
-            K.colsum(dY, acc_into=_grad_of(b))
-        else:
-            dB = K.colsum(dY)
-    return dW, dB
+def _ff_grads(dY, x, w, b, want_w, want_b):
+    """(dW, dB) of y = x w^T + b; accumulated straight into param.grad under gradient-accumulation fusion (a tied weight then collects
+    every layer's contribution in place), else returned"""
+    return (_matmul_wgrad(dY, x, w) if want_w else None), (_param_colsum(dY, b) if want_b else None)
 
 
 class _FastAttention(torch.autograd.Function):
@@ -1789,18 +1800,18 @@ class _FastAttention(torch.autograd.Function):
         ng = ctx.needs_input_grad
         dT2 = dout.contiguous().view(B * T, Cc)
         dWV = _ff_dgrad(dT2, wt)
-        dWt, dbt = _ff_wgrad(dT2, WV, wt, bt, ng[11], ng[12])
+        dWt, dbt = _ff_grads(dT2, WV, wt, bt, ng[11], ng[12])
         dQ, dpk = K.fastformer_bcast_bwd(dWV, Q, pk, B, T, dX_in=dT2, out=None)          # dQ = dT2 (residual) + dWV * pk
         dQK, dsk = K.fastformer_pool_bwd(dpk, pk, stk, sk, QK, lens, B, T, H, div)
         dQK_lin = _ff_dgrad(dsk, wkl)
-        dWkl, dbkl = _ff_wgrad(dsk, QK, wkl, bkl, ng[9], ng[10])
+        dWkl, dbkl = _ff_grads(dsk, QK, wkl, bkl, ng[9], ng[10])
         dK, dpq = K.fastformer_bcast_bwd(dQK, Kt, pq, B, T, dY2=dQK_lin)
         dQ, dsq = K.fastformer_pool_bwd(dpq, pq, stq, sq, Q, lens, B, T, H, div, dV_in=dQ)     # in place: dQ += alpha_q dpq
         dQ = _ff_dgrad(dsq, wql, R=dQ)
-        dWql, dbql = _ff_wgrad(dsq, Q, wql, bql, ng[7], ng[8])
+        dWql, dbql = _ff_grads(dsq, Q, wql, bql, ng[7], ng[8])
         dh = _ff_dgrad(dQ, wq, R=_ff_dgrad(dK, wk)) if ng[0] else None
-        dWq, dbq = _ff_wgrad(dQ, hm, wq, bq, ng[3], ng[4])
-        dWk, dbk = _ff_wgrad(dK, hm, wk, bk, ng[5], ng[6])
+        dWq, dbq = _ff_grads(dQ, hm, wq, bq, ng[3], ng[4])
+        dWk, dbk = _ff_grads(dK, hm, wk, bk, ng[5], ng[6])
         return (dh.view(B, T, Cc) if dh is not None else None, None, None, dWq, dbq, dWk, dbk, dWql, dbql, dWkl, dbkl, dWt, dbt)
 
 
@@ -1827,5 +1838,5 @@ class _ResDrop(torch.autograd.Function):
 def residual_dropout(x, t, rowscale=None, p_drop=0.0, drop=None):
     """y = rowscale * (x + dropout(t)): `x = x + PreNorm(fn)(x)` then `masked_fill(pad, 0)` when fn ends in a dropout that the sub-layer's
     last GEMM cannot apply itself (Fastformer: the query residual sits inside the dropout)"""
-    seed, off = (drop.seed, drop.next_offset()) if (drop is not None and p_drop > 0) else (None, 0)
-    return _ResDrop.apply(x, t, rowscale, p_drop if seed is not None else 0.0, seed, off)
+    p_drop, seed, off = _drop_args(p_drop, drop)
+    return _ResDrop.apply(x, t, rowscale, p_drop, seed, off)

@@ -86,14 +86,14 @@ def test_one_term_weight_gradient_launch_is_the_product_of_the_bf16_rounded_oper
 
 
 def _ffn_layer(autocast):
-    """the decoder FFN conv at full size through ops.linear_conv (forward + backward), with and without autocast"""
+    """the decoder FFN conv at full size through ops.conv1d (forward + backward), with and without autocast"""
     torch.manual_seed(7)
     B, T, cin, cout, k = 16, 1024, 256, 1024, 9
     x = torch.randn(B, T, cin, device=DEV, requires_grad=True)
     w = torch.nn.Parameter((torch.randn(cout, k, cin, device=DEV) * 0.02).permute(0, 2, 1))      # GEMM-major memory, Conv1d shape
     b = torch.nn.Parameter(torch.zeros(cout, device=DEV))
     with torch.amp.autocast("cuda", enabled=autocast):
-        y = ops._LinearConv.apply(x, w, b, None, None, ops.ACT_NONE, 1.0, 0.0, None, 0, k, None, 0)
+        y = ops.conv1d(x, w, b)
     g = torch.randn(B, T, cout, generator=torch.Generator().manual_seed(8)).to(DEV)
     ops.set_grad_accumulation_fusion(False)          # plain autograd: the weight gradient comes back as a tensor
     y.backward(g)
