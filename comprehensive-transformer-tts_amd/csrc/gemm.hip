@@ -1,14 +1,16 @@
-// fp32 MFMA GEMM for gfx950 with implicit-im2col operand views and a fused epilogue.
+// fp32 MFMA GEMM for gfx950 with implicit-im2col operand views and a fused epilogue: the tile-per-workgroup kernels.
 //
-// Tiling: 256 threads = 4 waves (2 x 2); block tile BM x BN x 32, wave tile (BM/2) x (BN/2) as
-// (BM/64) x (BN/64) MFMA tiles of v_mfma_f32_32x32x2_f32 (exact fp32, 64 FLOP/clk/SIMD = the
-// fp32 roofline on CDNA4).  K is consumed 32 at a time; inside a K-block the MFMA's two
-// k-lanes (lane>>5) take k = h*16 + j so that a K-contiguous operand is fetched from LDS as four
-// ds_read_b128 per 32-row tile (row stride 36 floats -> conflict-free 16-lane groups).
-// Global->LDS staging goes through registers (prefetch of K-block i+1 is issued before the
-// MFMAs of block i), which lets the loader apply the conv time-boundary predicate and the
-// batch/length limits for free.  blockIdx.x is remapped so that each XCD owns a contiguous
-// run of tiles (tiles that share an A panel hit the same L2).
+// gemm_tile_kernel: 256 threads = 4 waves (2 x 2, or 4 x 1 for 32-column tiles); block tile BM x BN x BK, wave tile as 32 x 32 MFMA
+// tiles of v_mfma_f32_32x32x2_f32 (exact fp32, 64 FLOP/clk/SIMD = the fp32 roofline on CDNA4).  K is consumed BK at a time; inside a
+// 32-deep sub-block the MFMA's two k-lanes (lane>>5) take k = h*16 + j so that a K-contiguous operand is fetched from LDS as four
+// ds_read_b128 per 32-row tile (row stride 36 floats -> conflict-free 16-lane groups).  Global->LDS staging goes through registers
+// (prefetch of K-block i+1 is issued before the MFMAs of block i), which lets the loader apply the conv time-boundary predicate and the
+// batch/length limits for free.  ONE body serves every way of fetching the operands (Fetch: scalar or 16-byte pointer loads, buffer
+// loads, buffer loads with per-batch limits); what a fetch policy changes besides its loaders is listed in FetchTraits.
+// gemm_buf_k2_kernel (two wave groups split the reduction), gemm_x6_kernel and gemm_x6tn_kernel (fp32 products on the bf16 matrix pipe)
+// have main loops of their own; their prologues and the split-K reduce use the same helpers: rows_in_padding (the padding rule),
+// gemm_split_range (gemm_common.h: the K range of a split), batch_limits, xcd_tile_order, zero_tile and zero_outside_limits.
+// Host side: tile_plan / gemm_route decide which kernel takes a descriptor, ctts_gemm launches it.
 #include "ctts_common.h"
 #include "gemm_common.h"
 #include <stdlib.h>
@@ -27,6 +29,87 @@ constexpr int KC_LD = BK + 4;     // row stride of K-contiguous operand tiles: 3
 constexpr int KCH = BK / 4;       // float4 chunks per tile row
 static_assert(BK == 32 || BK == 64, "BK must be 32 or 64");
 
+// ---- what every tile kernel of this file decides the same way ---------------------------------------------------------------------
+
+// Rows first .. last of a (b, t) row space with row_T rows per utterance lie wholly in the padding of ONE utterance (beyond its length
+// plus the halo).  Output rows there are defined as zero; reduction rows there contribute zero.
+__device__ __forceinline__ bool rows_in_padding(const int32_t* row_lens, int row_T, int row_halo, int first, int last) {
+  const int b0 = first / row_T;
+  return b0 == last / row_T && (first - b0 * row_T) >= row_lens[b0] + row_halo;
+}
+
+// The extents of batch z0: M x N x K, each cut at the batch's valid length where the descriptor limits it (`apply`: the caller's
+// kernel honours d.lens at all)
+__device__ __forceinline__ void batch_limits(const ctts_gemm_desc& d, int z0, bool apply, int& Mv, int& Nv, int& Kv) {
+  Mv = d.M; Nv = d.N; Kv = d.K;
+  if (apply && d.lens) {
+    const int L = d.lens[z0];
+    if (d.lim_m) Mv = min(Mv, L);
+    if (d.lim_n) Nv = min(Nv, L);
+    if (d.lim_k) Kv = min(Kv, L);
+  }
+}
+
+// The K range of this workgroup: everything, or the share of its split (k_granule = `granule`).  false: an empty share, nothing to write.
+__device__ __forceinline__ bool split_k_range(const ctts_gemm_desc& d, int Kv, int granule, int split, int& k_begin, int& k_end) {
+  k_begin = 0; k_end = Kv;
+  if (d.split_k > 1) {
+    const GemmSplitRange s = gemm_split_range(Kv, d.split_k, granule, split);
+    k_begin = s.k_begin; k_end = s.k_end;
+    if (k_begin >= k_end) return false;
+  }
+  return true;
+}
+
+// XCD-contiguous tile order (bijective for any grid size): workgroup blockIdx.x runs on XCD blockIdx.x % 8, so each XCD gets a
+// contiguous run of tiles (tiles that share an A panel hit the same L2).  scramble: the m-tiles are visited in an odd-prime stride
+// permutation - with padded-row skipping the empty tiles of the short sequences would otherwise all land on the same XCD.
+__device__ __forceinline__ void xcd_tile_order(int nwg, int tiles_n, bool scramble, int& wg, int& tm) {
+  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int tiles_m = nwg / tiles_n;
+  tm = wg / tiles_n;
+  if (scramble) {
+    const int P = (tiles_m % 37) ? 37 : ((tiles_m % 41) ? 41 : 43);
+    tm = (int)(((long)tm * P) % tiles_m);
+  }
+}
+
+// ctts_gemm_desc.tile_map is a device-built schedule, or this sentinel: plain blockIdx order (CTTS_NATURAL_ORDER / CTTS_TN_NATURAL)
+__device__ __forceinline__ bool natural_order(const ctts_gemm_desc& d) { return d.tile_map == reinterpret_cast<const int32_t*>(1); }
+
+// zeros into the [nrows, ncols] block of C at (row0, col0), and of Z where a forward epilogue would have stored it (whole workgroup)
+__device__ __forceinline__ void zero_tile(const ctts_gemm_desc& d, float* C, int row0, int col0, int nrows, int ncols) {
+  for (int e = threadIdx.x; e < nrows * ncols; e += 256) {
+    const int r = e / ncols, c = e - r * ncols;
+    C[(long)(row0 + r) * d.ldc + col0 + c] = 0.f;
+    if (d.Z && !d.epi_bwd) d.Z[(long)(row0 + r) * d.ldz + col0 + c] = 0.f;
+  }
+}
+
+// a tile whose rows row0 .. lie wholly in the padding of one utterance: zero-filled here - no operand traffic, no MFMA - and true
+__device__ __forceinline__ bool padded_tile_zeroed(const ctts_gemm_desc& d, float* C, int row0, int col0, int BM, int ncols, int Mv) {
+  const int last = min(row0 + BM, Mv) - 1;
+  if (!rows_in_padding(d.row_lens, d.row_T, d.row_halo, row0, last)) return false;
+  zero_tile(d, C, row0, col0, last - row0 + 1, ncols);
+  return true;
+}
+
+// "write everything" (split_overwrite) on an unsplit batched launch with per-batch limits: what the BM x BN tile at (row0, col0) covers
+// of the batch's [M, N] block but outside its limits Mv x Nv is WRITTEN as zero (the caller passes an uninitialised C: no fill launch per
+// attention product; the epilogue never stores there).  whole: the tile lies beyond the limits altogether.
+__device__ __forceinline__ void zero_outside_limits(const ctts_gemm_desc& d, float* C, int row0, int col0, int BM, int BN, int Mv, int Nv,
+                                                    bool whole) {
+  const int nrows = min(BM, d.M - row0), ncols = min(BN, d.N - col0);
+  for (int e = threadIdx.x; e < nrows * ncols; e += 256) {
+    const int r = e / ncols, c = e - r * ncols;
+    if (whole || row0 + r >= Mv || col0 + c >= Nv) C[(long)(row0 + r) * d.ldc + col0 + c] = 0.f;
+  }
+}
+
+// ---- operand loaders: one interface.  init(base, ld, ext0, ext_lim, conv view, tid) once per tile - the operand's (batch) base pointer
+// and leading dimension, the tile's first row / column along the non-reduction extent and that extent's limit; load(k0, k_end, regs)
+// fetches K-block k0 (cut at k_end) into staging registers; store(lds, regs) writes them to the LDS tile.
 struct ConvView {
   int T, pad, cin;
 };
@@ -37,45 +120,37 @@ struct LoaderKC {
   static constexpr int NV = ROWS * BK / 4 / 256;
   const float* base;
   long ld;
-  int row0, row_lim, kq;
-  bool vec;
+  int row0, row_lim, kq, tid;
   ConvView cv;
   int trow[NV];
-  __device__ void init(const float* p, long ld_, int row0_, int row_lim_, bool vec_, ConvView cv_) {
-    base = p; ld = ld_; row0 = row0_; row_lim = row_lim_; vec = vec_; cv = cv_;
-    kq = (threadIdx.x % KCH) << 2;
+  __device__ __forceinline__ void init(const float* p, long ld_, int row0_, int row_lim_, ConvView cv_, int tid_) {
+    base = CONV ? p - (long)cv_.pad * cv_.cin : p;      // conv: im2col row starts pad rows earlier
+    ld = ld_; row0 = row0_; row_lim = row_lim_; cv = cv_; tid = tid_;
+    kq = (tid % KCH) << 2;
     if (CONV) {
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
-        int gr = row0 + ((threadIdx.x + i * 256) / KCH);
+        int gr = row0 + ((tid + i * 256) / KCH);
         trow[i] = gr % cv.T;
       }
     }
   }
   __device__ __forceinline__ void load(int k0, int k_end, float4 (&r)[NV]) const {
     const int gk = k0 + kq;
-    int tap = 0;
-    if (CONV) tap = gk / cv.cin - cv.pad;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int gr = row0 + ((threadIdx.x + i * 256) / KCH);
+      const int gr = row0 + ((tid + i * 256) / KCH);
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (gr < row_lim && gk < k_end) {
         const float* p = base + (long)gr * ld + gk;
-        bool ok = true;
-        if (CONV) { int tt = trow[i] + tap; ok = (tt >= 0) && (tt < cv.T); }
-        if (vec && gk + 3 < k_end) {
-          if (ok) v = *reinterpret_cast<const float4*>(p);
-        } else {
-          float e[4] = {0.f, 0.f, 0.f, 0.f};
+        float e[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            bool okq = (gk + q < k_end);
-            if (CONV && okq) { int tt = trow[i] + (gk + q) / cv.cin - cv.pad; okq = (tt >= 0) && (tt < cv.T); }
-            if (okq) e[q] = p[q];
-          }
-          v = make_float4(e[0], e[1], e[2], e[3]);
+        for (int q = 0; q < 4; ++q) {
+          bool okq = (gk + q < k_end);
+          if (CONV && okq) { int tt = trow[i] + (gk + q) / cv.cin - cv.pad; okq = (tt >= 0) && (tt < cv.T); }
+          if (okq) e[q] = p[q];
         }
+        v = make_float4(e[0], e[1], e[2], e[3]);
       }
       r[i] = v;
     }
@@ -83,7 +158,7 @@ struct LoaderKC {
   __device__ __forceinline__ void store(float* s, const float4 (&r)[NV]) const {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int row = (threadIdx.x + i * 256) / KCH;
+      const int row = (tid + i * 256) / KCH;
       *reinterpret_cast<float4*>(s + row * KC_LD + kq) = r[i];
     }
   }
@@ -96,18 +171,16 @@ struct LoaderRC {
   static constexpr int LD = COLS + 4;
   const float* base;
   long ld;
-  int col0, col_lim;
-  bool vec;
+  int col0, col_lim, tid;
   ConvView cv;
-  int tap[1];
-  __device__ void init(const float* p, long ld_, int col0_, int col_lim_, bool vec_, ConvView cv_) {
-    base = p; ld = ld_; col0 = col0_; col_lim = col_lim_; vec = vec_; cv = cv_;
-    tap[0] = 0;
+  __device__ __forceinline__ void init(const float* p, long ld_, int col0_, int col_lim_, ConvView cv_, int tid_) {
+    base = CONV ? p - (long)cv_.pad * cv_.cin : p;
+    ld = ld_; col0 = col0_; col_lim = col_lim_; cv = cv_; tid = tid_;
   }
   __device__ __forceinline__ void load(int k0, int k_end, float4 (&r)[NV]) const {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int f = threadIdx.x + i * 256;
+      const int f = tid + i * 256;
       const int k = f / (COLS / 4);
       const int cq = (f % (COLS / 4)) << 2;
       const int gk = k0 + k, gc = col0 + cq;
@@ -116,20 +189,14 @@ struct LoaderRC {
         const float* p = base + (long)gk * ld + gc;
         int trow = 0;
         if (CONV) trow = gk % cv.T;
-        if (vec && gc + 3 < col_lim) {
-          bool ok = true;
-          if (CONV) { int tt = trow + gc / cv.cin - cv.pad; ok = (tt >= 0) && (tt < cv.T); }
-          if (ok) v = *reinterpret_cast<const float4*>(p);
-        } else {
-          float e[4] = {0.f, 0.f, 0.f, 0.f};
+        float e[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            bool okq = (gc + q < col_lim);
-            if (CONV && okq) { int tt = trow + (gc + q) / cv.cin - cv.pad; okq = (tt >= 0) && (tt < cv.T); }
-            if (okq) e[q] = p[q];
-          }
-          v = make_float4(e[0], e[1], e[2], e[3]);
+        for (int q = 0; q < 4; ++q) {
+          bool okq = (gc + q < col_lim);
+          if (CONV && okq) { int tt = trow + (gc + q) / cv.cin - cv.pad; okq = (tt >= 0) && (tt < cv.T); }
+          if (okq) e[q] = p[q];
         }
+        v = make_float4(e[0], e[1], e[2], e[3]);
       }
       r[i] = v;
     }
@@ -137,7 +204,7 @@ struct LoaderRC {
   __device__ __forceinline__ void store(float* s, const float4 (&r)[NV]) const {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int f = threadIdx.x + i * 256;
+      const int f = tid + i * 256;
       const int k = f / (COLS / 4);
       const int cq = (f % (COLS / 4)) << 2;
       *reinterpret_cast<float4*>(s + k * LD + cq) = r[i];
@@ -147,8 +214,8 @@ struct LoaderRC {
 
 
 // ---------------------------------------------------------------------------------------------
-// Branch-free loaders for the aligned case (VEC): every 16-byte chunk is fetched UNCONDITIONALLY
-// from an in-bounds address (invalid chunks read a safe dummy address) and the validity mask is
+// Branch-free loaders for the aligned case (Fetch::Vec): every 16-byte chunk is fetched UNCONDITIONALLY
+// from an in-bounds address (invalid chunks read a safe dummy address: the operand's base) and the validity mask is
 // applied only when the registers are written to LDS.  Nothing between the global_load and the
 // ds_write consumes the loaded value, so hipcc keeps the loads in flight across the MFMA block
 // (a select / branch join on the loaded value would force an s_waitcnt vmcnt(0) before the MFMAs).
@@ -165,16 +232,18 @@ struct VLoaderKC {
   static constexpr int NV = ROWS * BK / 4 / 256;
   const float* base; const float* safe;
   long ld;
-  int row0, row_lim, kq;
+  int row0, row_lim, kq, tid;
   ConvView cv;
   int trow[NV];
   int nval[NV];
-  __device__ void init(const float* p, const float* safe_, long ld_, int row0_, int row_lim_, ConvView cv_) {
-    base = p; safe = safe_; ld = ld_; row0 = row0_; row_lim = row_lim_; cv = cv_;
-    kq = (threadIdx.x % KCH) << 2;
+  __device__ __forceinline__ void init(const float* p, long ld_, int row0_, int row_lim_, ConvView cv_, int tid_) {
+    safe = p;
+    base = CONV ? p - (long)cv_.pad * cv_.cin : p;
+    ld = ld_; row0 = row0_; row_lim = row_lim_; cv = cv_; tid = tid_;
+    kq = (tid % KCH) << 2;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int gr = row0 + ((threadIdx.x + i * 256) / KCH);
+      const int gr = row0 + ((tid + i * 256) / KCH);
       trow[i] = CONV ? gr % cv.T : 0;
       nval[i] = 0;
     }
@@ -186,7 +255,7 @@ struct VLoaderKC {
     const int nk = min(4, k_end - gk);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int gr = row0 + ((threadIdx.x + i * 256) / KCH);
+      const int gr = row0 + ((tid + i * 256) / KCH);
       bool ok = (gr < row_lim) && (nk > 0);
       if (CONV) { const int tt = trow[i] + tap; ok = ok && (tt >= 0) && (tt < cv.T); }
       const float* p = ok ? base + (long)gr * ld + gk : safe;
@@ -197,7 +266,7 @@ struct VLoaderKC {
   __device__ __forceinline__ void store(float* s, const float4 (&r)[NV]) const {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int row = (threadIdx.x + i * 256) / KCH;
+      const int row = (tid + i * 256) / KCH;
       *reinterpret_cast<float4*>(s + row * KC_LD + kq) = mask4(r[i], nval[i]);
     }
   }
@@ -209,18 +278,20 @@ struct VLoaderRC {
   static constexpr int LD = COLS + 4;
   const float* base; const float* safe;
   long ld;
-  int col0, col_lim;
+  int col0, col_lim, tid;
   ConvView cv;
   int nval[NV];
-  __device__ void init(const float* p, const float* safe_, long ld_, int col0_, int col_lim_, ConvView cv_) {
-    base = p; safe = safe_; ld = ld_; col0 = col0_; col_lim = col_lim_; cv = cv_;
+  __device__ __forceinline__ void init(const float* p, long ld_, int col0_, int col_lim_, ConvView cv_, int tid_) {
+    safe = p;
+    base = CONV ? p - (long)cv_.pad * cv_.cin : p;
+    ld = ld_; col0 = col0_; col_lim = col_lim_; cv = cv_; tid = tid_;
 #pragma unroll
     for (int i = 0; i < NV; ++i) nval[i] = 0;
   }
   __device__ __forceinline__ void load(int k0, int k_end, float4 (&r)[NV]) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int f = threadIdx.x + i * 256;
+      const int f = tid + i * 256;
       const int k = f / (COLS / 4);
       const int cq = (f % (COLS / 4)) << 2;
       const int gk = k0 + k, gc = col0 + cq;
@@ -235,7 +306,7 @@ struct VLoaderRC {
   __device__ __forceinline__ void store(float* s, const float4 (&r)[NV]) const {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int f = threadIdx.x + i * 256;
+      const int f = tid + i * 256;
       const int k = f / (COLS / 4);
       const int cq = (f % (COLS / 4)) << 2;
       *reinterpret_cast<float4*>(s + k * LD + cq) = mask4(r[i], nval[i]);
@@ -244,11 +315,12 @@ struct VLoaderRC {
 };
 
 // ---------------------------------------------------------------------------------------------
-// Buffer-descriptor loaders (VEC = 3) for the large GEMMs without per-batch length limits.
+// Buffer-descriptor loaders (Fetch::Buffer / BufferPartial).
 // The operand is addressed as  SRD(base, 2 GiB window) + 32-bit byte offset.  A masked-out chunk simply
 // gets the offset 0x80000000, which the hardware bounds check answers with zeros: no zero page, no select
 // on the loaded data, no 64-bit pointer arithmetic - per chunk and K-block the address work is one add and
 // (conv / K-tail only) one compare + v_cndmask.  Host guarantees every valid offset is < 2^31 bytes.
+// PARTIAL: extents that are no multiple of 4 (per-batch limits) - the chunk that straddles the limit is cut when it is stored.
 typedef unsigned int ctts_u32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned CTTS_OOB = 0x80000000u;
 
@@ -260,11 +332,13 @@ __device__ __forceinline__ float4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, unsign
 template <int ROWS, bool CONV, bool PARTIAL>
 struct BLoaderKC {
   static constexpr int NV = ROWS * BK / 4 / 256;
+  __amdgpu_buffer_rsrc_t rsrc;
   unsigned boff[NV];      // byte offset of (row, kq) relative to the descriptor base, or CTTS_OOB
   int trow[NV];
   int kq, tid, T, cin, pad;
   int nk_cur;             // PARTIAL: valid elements of this thread's chunk in the staged K-block (same for all rows)
-  __device__ void init(long ld, int row0, int row_lim, ConvView cv, int tid_) {
+  __device__ __forceinline__ void init(const float* p, long ld, int row0, int row_lim, ConvView cv, int tid_) {
+    rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, 0x7FFFFFFE, 0x00020000);
     tid = tid_; T = cv.T; cin = cv.cin; pad = cv.pad;
     kq = (tid % KCH) << 2;
 #pragma unroll
@@ -276,7 +350,7 @@ struct BLoaderKC {
     }
     nk_cur = 4;
   }
-  __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t rsrc, int k0, int k_end, float4 (&r)[NV]) {
+  __device__ __forceinline__ void load(int k0, int k_end, float4 (&r)[NV]) {
     const int gk = k0 + kq;
     const bool kok = gk < k_end;                       // K tail: chunk fully masked, or (PARTIAL) cut at k_end
     if (PARTIAL) nk_cur = min(4, k_end - gk);
@@ -304,12 +378,14 @@ template <int COLS, bool CONV, bool PARTIAL>
 struct BLoaderRC {
   static constexpr int NV = COLS * BK / 4 / 256;
   static constexpr int LD = COLS + 4;
+  __amdgpu_buffer_rsrc_t rsrc;
   unsigned boff[NV];      // byte offset of (k_local row, column chunk) at k0 = 0, or CTTS_OOB
   int ctap[NV];           // CONV: gc / cin - pad (loop invariant)
   unsigned ldb4;          // row stride in bytes
   int tid, T;
   int ncol[NV];           // PARTIAL: valid elements of the chunk along the contiguous dim (loop invariant)
-  __device__ void init(long ld, int col0, int col_lim, ConvView cv, int tid_) {
+  __device__ __forceinline__ void init(const float* p, long ld, int col0, int col_lim, ConvView cv, int tid_) {
+    rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, 0x7FFFFFFE, 0x00020000);
     tid = tid_; T = cv.T; ldb4 = (unsigned)(ld * 4);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -322,7 +398,7 @@ struct BLoaderRC {
       ncol[i] = PARTIAL ? min(4, col_lim - gc) : 4;
     }
   }
-  __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t rsrc, int k0, int k_end, float4 (&r)[NV]) const {
+  __device__ __forceinline__ void load(int k0, int k_end, float4 (&r)[NV]) const {
     const unsigned k0off = (unsigned)k0 * ldb4;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -342,19 +418,43 @@ struct BLoaderRC {
   }
 };
 
-template <bool KC, int EXT, bool CONV, bool PARTIAL>
-struct BLoaderSel { using type = BLoaderKC<EXT, CONV, PARTIAL>; };
-template <int EXT, bool CONV, bool PARTIAL>
-struct BLoaderSel<false, EXT, CONV, PARTIAL> { using type = BLoaderRC<EXT, CONV, PARTIAL>; };
+// ---- how the tile kernel fetches its operands, and everything else that follows from that choice
+enum class Fetch {
+  Scalar,           // dword pointer loads: any alignment, any extent (operands beyond the 2 GiB buffer window included)
+  Vec,              // 16-byte pointer loads: aligned operands the buffer window does not cover
+  Buffer,           // 16-byte buffer loads
+  BufferPartial,    // ... with per-batch length limits (d.lens): the attention products
+};
 
-template <bool KC, int EXT, bool CONV, bool VEC>
-struct LoaderSel { using type = LoaderKC<EXT, CONV>; };
-template <int EXT, bool CONV>
-struct LoaderSel<false, EXT, CONV, false> { using type = LoaderRC<EXT, CONV>; };
-template <int EXT, bool CONV>
-struct LoaderSel<true, EXT, CONV, true> { using type = VLoaderKC<EXT, CONV>; };
-template <int EXT, bool CONV>
-struct LoaderSel<false, EXT, CONV, true> { using type = VLoaderRC<EXT, CONV>; };
+template <Fetch F>
+struct FetchTraits {
+  static constexpr bool kBuffer = F == Fetch::Buffer || F == Fetch::BufferPartial;
+  // d.lens limits the extents of a batch: pointer fetch whenever d.lens is set; buffer fetch only in the partial variant, which
+  // the launcher picks exactly when d.lens is set (the plain variant's loaders cannot cut a chunk) ...
+  static constexpr bool kLensLimits = F != Fetch::Buffer;
+  // ... so that variant takes the limits as given where the pointer kernels ask the descriptor
+  static constexpr bool kLensGiven = F == Fetch::BufferPartial;
+  // tile orders besides the XCD-contiguous one - device-built tile_map schedule, tile_group_n, the natural-order sentinel: only
+  // tile_plan's buffer routes are set up with them; pointer fetch always uses the XCD remap
+  static constexpr bool kTileOrders = kBuffer;
+  // always plain blockIdx order: the valid tiles of a short utterance are its FIRST rows / columns, and the XCD-contiguous remap would
+  // put all of them on the first XCDs
+  static constexpr bool kNaturalOrder = F == Fetch::BufferPartial;
+  // a tile the schedule lists as active skips the padded-tile test (the schedule was built with the same rule)
+  static constexpr bool kTrustSchedule = kTileOrders;
+  // the loaders cut partly valid chunks when they store to LDS (the others fetch only valid elements, or whole chunks)
+  static constexpr bool kMaskAtStore = F == Fetch::Vec || F == Fetch::BufferPartial;
+  // split-K: a padded tile's zeros go to the partial matrix of the workgroup's own split (buffer) or to the batch's first (pointer);
+  // the reduce skips such tiles either way
+  static constexpr bool kPadFillOwnSplit = kBuffer;
+};
+
+template <Fetch F, bool KC, int EXT, bool CONV>
+using Loader = std::conditional_t<
+    FetchTraits<F>::kBuffer,
+    std::conditional_t<KC, BLoaderKC<EXT, CONV, FetchTraits<F>::kMaskAtStore>, BLoaderRC<EXT, CONV, FetchTraits<F>::kMaskAtStore>>,
+    std::conditional_t<F == Fetch::Vec, std::conditional_t<KC, VLoaderKC<EXT, CONV>, VLoaderRC<EXT, CONV>>,
+                       std::conditional_t<KC, LoaderKC<EXT, CONV>, LoaderRC<EXT, CONV>>>>;
 
 // fragment fetch for one 32-wide MFMA tile: 16 k-steps, lane (l31, h) gets element k = h*16 + j
 template <bool KC, int LD>
@@ -373,185 +473,9 @@ __device__ __forceinline__ void fetch_frag(const float* s, int ext0, int l31, in
   }
 }
 
-template <int BM, int BN, bool A_KC, bool B_KC, bool CONV, bool VEC>
-__global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_kernel(const ctts_gemm_desc d) {
-  constexpr int WM = BM / 2, WN = BN / 2, MT = WM / 32, NT = WN / 32;
-  constexpr int A_LD = A_KC ? KC_LD : BM + 4;
-  constexpr int B_LD = B_KC ? KC_LD : BN + 4;
-  constexpr int A_SZ = A_KC ? BM * KC_LD : BK * (BM + 4);
-  constexpr int B_SZ = B_KC ? BN * KC_LD : BK * (BN + 4);
-  __shared__ __attribute__((aligned(16))) float smem[A_SZ + B_SZ];
-  float* sA = smem;
-  float* sB = smem + A_SZ;
-
-  // ---- batch / split decode
-  const int z = blockIdx.z;
-  const int split = blockIdx.y;                         // K split (grid.y = split_k, 1 when off); z = batch index
-  const int z0 = z / d.nb1, z1 = z - z0 * d.nb1;
-  int Mv = d.M, Nv = d.N, Kv = d.K;
-  if (d.lens) {
-    const int L = d.lens[z0];
-    if (d.lim_m) Mv = min(Mv, L);
-    if (d.lim_n) Nv = min(Nv, L);
-    if (d.lim_k) Kv = min(Kv, L);
-  }
-  // ---- XCD-aware tile mapping (bijective for any grid size)
-  const int tiles_n = (d.N + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-  // m-tiles are visited in a scrambled order (odd-prime stride permutation): with padded-row skipping the
-  // empty tiles of the short sequences would otherwise all land on the same XCD (static block->XCD map)
-  const int tiles_m = nwg / tiles_n;
-  int tm = wg / tiles_n;
-  {
-    const int P = (tiles_m % 37) ? 37 : ((tiles_m % 41) ? 41 : 43);
-    tm = (int)(((long)tm * P) % tiles_m);
-  }
-  const int row0 = tm * BM, col0 = (wg % tiles_n) * BN;
-  {
-    // "write everything" (split_overwrite) on an unsplit launch with per-batch limits: the part of the batch's [M, N] block outside the
-    // limits is written as zero by the tile that covers it (same rule as gemm_buf_kernel)
-    const bool zero_outside = d.lens && d.split_overwrite && d.split_k <= 1;
-    const bool beyond = row0 >= Mv || col0 >= Nv;
-    if (zero_outside && row0 < d.M && col0 < d.N && (beyond || row0 + BM > Mv || col0 + BN > Nv)) {
-      float* Cz = d.C + z0 * d.sC0 + z1 * d.sC1;
-      const int nrows = min(BM, d.M - row0), ncols = min(BN, d.N - col0);
-      for (int e = threadIdx.x; e < nrows * ncols; e += 256) {
-        const int r = e / ncols, c = e - r * ncols;
-        if (row0 + r >= Mv || col0 + c >= Nv) Cz[(long)(row0 + r) * d.ldc + col0 + c] = 0.f;
-      }
-    }
-    if (beyond) return;
-  }
-
-  if (A_KC && d.row_lens) {  // whole tile of padded rows -> zeros, no operand traffic, no MFMA
-    const int last = min(row0 + BM, Mv) - 1;
-    const int b0 = row0 / d.row_T, b1 = last / d.row_T;
-    if (b0 == b1 && (row0 - b0 * d.row_T) >= d.row_lens[b0] + d.row_halo) {
-      float* Cz = d.C + z0 * d.sC0 + z1 * d.sC1;
-      const int ncols = min(BN, Nv - col0), nrows = last - row0 + 1;
-      for (int e = threadIdx.x; e < nrows * ncols; e += 256) {
-        const int r = e / ncols, c = e - r * ncols;
-        Cz[(long)(row0 + r) * d.ldc + col0 + c] = 0.f;
-        if (d.Z && !d.epi_bwd) d.Z[(long)(row0 + r) * d.ldz + col0 + c] = 0.f;
-      }
-      return;
-    }
-  }
-  int k_begin = 0, k_end = Kv;
-  if (d.split_k > 1) {
-    int chunk = ((Kv + d.split_k - 1) / d.split_k + BK - 1) / BK * BK;
-    k_begin = split * chunk;
-    k_end = min(Kv, k_begin + chunk);
-    if (k_begin >= k_end) return;
-  }
-
-  const float* Ab = d.A + z0 * d.sA0 + z1 * d.sA1;
-  const float* Bb = d.B + z0 * d.sB0 + z1 * d.sB1;
-  float* Cb = d.C + z0 * d.sC0 + z1 * d.sC1;
-  if (d.split_k > 1) Cb += (long)split * d.M * d.ldc;      // split-K: C is the partial matrix P_split of the workspace (ctts_gemm rewrote the descriptor)
-  const float* Asafe = Ab;   // in-bounds, 16-B aligned dummy addresses for masked-out chunks (VEC loaders)
-  const float* Bsafe = Bb;
-  ConvView cv{d.conv_T, d.conv_pad, d.conv_cin};
-  ConvView nocv{1, 0, 1};
-  constexpr bool CONV_A = CONV && A_KC;
-  constexpr bool CONV_B = CONV && !A_KC && !B_KC;
-  if (CONV_A) Ab -= (long)d.conv_pad * d.conv_cin;
-  if (CONV_B) Bb -= (long)d.conv_pad * d.conv_cin;
-
-  using LA = typename LoaderSel<A_KC, BM, CONV_A, VEC>::type;
-  using LB = typename LoaderSel<B_KC, BN, CONV_B, VEC>::type;
-  LA la; LB lb;
-  if constexpr (VEC) {
-    la.init(Ab, Asafe, d.lda, row0, Mv, CONV_A ? cv : nocv);
-    lb.init(Bb, Bsafe, d.ldb, col0, Nv, CONV_B ? cv : nocv);
-  } else {
-    la.init(Ab, d.lda, row0, Mv, false, CONV_A ? cv : nocv);
-    lb.init(Bb, d.ldb, col0, Nv, false, CONV_B ? cv : nocv);
-  }
-
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int l31 = lane & 31, h = lane >> 5;
-  const int wm0 = (wave >> 1) * WM, wn0 = (wave & 1) * WN;
-
-  floatx16 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // weight-gradient reductions run over (b,t) rows: K-blocks that lie entirely in the padding of one
-  // sequence contribute exactly zero (dZ is zero there) and are skipped (block-uniform decision)
-  constexpr bool KSKIP = !A_KC && !B_KC;
-  auto kblock_active = [&](int k0) -> bool {
-    if (!KSKIP || !d.row_lens) return true;
-    const int lastk = min(k0 + BK, k_end) - 1;
-    const int b0 = k0 / d.row_T;
-    return !(b0 == lastk / d.row_T && (k0 - b0 * d.row_T) >= d.row_lens[b0] + d.row_halo);
-  };
-  float4 ra[LA::NV], rb[LB::NV];
-  bool act_cur = kblock_active(k_begin);
-  if (act_cur) {
-    la.load(k_begin, k_end, ra);
-    lb.load(k_begin, k_end, rb);
-    la.store(sA, ra);
-    lb.store(sB, rb);
-  }
-  __syncthreads();
-
-  for (int k0 = k_begin; k0 < k_end; k0 += BK) {
-    const bool has_next = (k0 + BK) < k_end;
-    const bool act_next = has_next && kblock_active(k0 + BK);
-    if (act_next) {
-      la.load(k0 + BK, k_end, ra);
-      lb.load(k0 + BK, k_end, rb);
-    }
-    if (act_cur) {
-#pragma unroll
-      for (int ksub = 0; ksub < BK; ksub += 32) {
-        float fa[MT][16], fb[NT][16];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) fetch_frag<A_KC, A_LD>(sA, wm0 + i * 32, l31, h, ksub, fa[i]);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) fetch_frag<B_KC, B_LD>(sB, wn0 + j * 32, l31, h, ksub, fb[j]);
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk)
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][kk], fb[j][kk], acc[i][j], 0, 0, 0);
-      }
-    }
-    if (KSKIP && !act_cur && !act_next) continue;   // nothing staged, nothing to publish: no barrier needed
-    __syncthreads();
-    if (act_next) {
-      la.store(sA, ra);
-      lb.store(sB, rb);
-    }
-    __syncthreads();
-    act_cur = act_next;
-  }
-
-  gemm_epilogue_auto<MT, NT>(d, acc, Cb, z, row0, col0, wm0, wn0, l31, h, Mv, Nv);
-}
-
-template <int BM, int BN, bool A_KC, bool B_KC, bool CONV, bool VEC>
-int launch(const ctts_gemm_desc& d, hipStream_t st) {
-  const int tiles = ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
-  const int nz = d.nb0 * d.nb1, ny = d.split_k > 1 ? d.split_k : 1;
-  dim3 grid(tiles, ny, nz);
-  hipLaunchKernelGGL((gemm_kernel<BM, BN, A_KC, B_KC, CONV, VEC>), grid, dim3(256), 0, st, d);
-  CTTS_CHECK_LAUNCH("ctts_gemm");
-  return 0;
-}
-
-// Same tiling / barrier structure as gemm_kernel, operands fetched through buffer descriptors.
-template <int BM, int BN, bool A_KC, bool B_KC, bool CONV, bool PARTIAL>
-__global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_buf_kernel(const ctts_gemm_desc d) {
+template <int BM, int BN, bool A_KC, bool B_KC, bool CONV, Fetch FETCH>
+__global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_tile_kernel(const ctts_gemm_desc d) {
+  using FT = FetchTraits<FETCH>;
   // 4 waves as 2 x 2, or 4 x 1 for the narrow tile (BN = 32: outputs with N <= 32, e.g. the d_head = 32 attention gradients)
   constexpr int WAVES_N = BN >= 64 ? 2 : 1, WAVES_M = 4 / WAVES_N;
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, MT = WM / 32, NT = WN / 32;
@@ -565,18 +489,14 @@ __global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_buf_kernel(const ct
   const int z = blockIdx.z;
   const int split = blockIdx.y;                         // K split (grid.y = split_k, 1 when off); z = batch index
   const int z0 = z / d.nb1, z1 = z - z0 * d.nb1;
-  int Mv = d.M, Nv = d.N, Kv = d.K;
-  if (PARTIAL && d.lens) {                // per-batch valid lengths (attention over non-padded tokens only)
-    const int L = d.lens[z0];
-    if (d.lim_m) Mv = min(Mv, L);
-    if (d.lim_n) Nv = min(Nv, L);
-    if (d.lim_k) Kv = min(Kv, L);
-  }
+  const bool limited = FT::kLensLimits && (FT::kLensGiven || d.lens);      // per-batch valid lengths (attention over non-padded tokens only)
+  int Mv, Nv, Kv;
+  batch_limits(d, z0, limited, Mv, Nv, Kv);
+  // ---- which tile
   const int tiles_n = (d.N + BN - 1) / BN;
-  const int nwg = gridDim.x;
   int wg, tm;
   bool scheduled_active = false;
-  if (BM == 64 && A_KC && d.tile_map && d.tile_map != reinterpret_cast<const int32_t*>(1)) {
+  if (FT::kTileOrders && BM == 64 && A_KC && d.tile_map && !natural_order(d)) {
     // device-built schedule: active m-tiles first, natural workgroup order (round-robin over the XCDs)
     wg = blockIdx.x;
     int r = wg / tiles_n;
@@ -587,76 +507,39 @@ __global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_buf_kernel(const ct
       wg = r * tiles_n + (x % ngroups) * g + i % g;
     }
     tm = d.tile_map[1 + r];
-    scheduled_active = r < d.tile_map[0];
-  } else if (PARTIAL || d.tile_map == reinterpret_cast<const int32_t*>(1)) {
-    // plain blockIdx order.  Always for per-batch length limits (attention): the valid tiles of a short utterance are its FIRST
-    // rows / columns, and the XCD-contiguous remap below would put all of them on the first XCDs.  Also the CTTS_NATURAL_ORDER knob.
+    scheduled_active = FT::kTrustSchedule && r < d.tile_map[0];
+  } else if (FT::kNaturalOrder || (FT::kTileOrders && natural_order(d))) {
     wg = blockIdx.x;
     tm = wg / tiles_n;
   } else {
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-    const int tiles_m = nwg / tiles_n;
-    tm = wg / tiles_n;
-    const int P = (tiles_m % 37) ? 37 : ((tiles_m % 41) ? 41 : 43);
-    tm = (int)(((long)tm * P) % tiles_m);
+    xcd_tile_order(gridDim.x, tiles_n, true, wg, tm);
   }
   const int row0 = tm * BM, col0 = (wg % tiles_n) * BN;
   float* Cb = d.C + z0 * d.sC0 + z1 * d.sC1;
-  // overwrite mode of an unsplit batched launch with per-batch limits: everything of the batch's [M, N] block outside the limits is
-  // WRITTEN as zero by the tile that covers it (the caller passes an uninitialised C: no fill launch per attention product)
-  const bool zero_outside = PARTIAL && d.split_overwrite && d.split_k <= 1;
+  // ---- tiles with nothing to multiply
+  const bool zero_outside = limited && d.split_overwrite && d.split_k <= 1;
   if (row0 >= Mv || col0 >= Nv) {
-    if (zero_outside && row0 < d.M && col0 < d.N) {
-      const int nrows = min(BM, d.M - row0), ncols = min(BN, d.N - col0);
-      for (int e = threadIdx.x; e < nrows * ncols; e += 256) {
-        const int r = e / ncols, c = e - r * ncols;
-        Cb[(long)(row0 + r) * d.ldc + col0 + c] = 0.f;
-      }
-    }
+    if (zero_outside && row0 < d.M && col0 < d.N) zero_outside_limits(d, Cb, row0, col0, BM, BN, Mv, Nv, true);
     return;
   }
-  if (zero_outside && (row0 + BM > Mv || col0 + BN > Nv)) {      // the part of a straddling tile beyond the limits (the epilogue never stores there)
-    const int nrows = min(BM, d.M - row0), ncols = min(BN, d.N - col0);
-    for (int e = threadIdx.x; e < nrows * ncols; e += 256) {
-      const int r = e / ncols, c = e - r * ncols;
-      if (row0 + r >= Mv || col0 + c >= Nv) Cb[(long)(row0 + r) * d.ldc + col0 + c] = 0.f;
-    }
-  }
-  if (d.split_k > 1) Cb += (long)split * d.M * d.ldc;      // split-K: C is the partial matrix P_split of the workspace (ctts_gemm rewrote the descriptor)
-  if (A_KC && d.row_lens && !scheduled_active) {
-    const int last = min(row0 + BM, Mv) - 1;
-    const int b0 = row0 / d.row_T, b1 = last / d.row_T;
-    if (b0 == b1 && (row0 - b0 * d.row_T) >= d.row_lens[b0] + d.row_halo) {
-      const int ncols = min(BN, Nv - col0), nrows = last - row0 + 1;
-      for (int e = threadIdx.x; e < nrows * ncols; e += 256) {
-        const int r = e / ncols, c = e - r * ncols;
-        Cb[(long)(row0 + r) * d.ldc + col0 + c] = 0.f;
-        if (d.Z && !d.epi_bwd) d.Z[(long)(row0 + r) * d.ldz + col0 + c] = 0.f;
-      }
-      return;
-    }
-  }
-  int k_begin = 0, k_end = Kv;
-  if (d.split_k > 1) {
-    int chunk = ((Kv + d.split_k - 1) / d.split_k + BK - 1) / BK * BK;
-    k_begin = split * chunk;
-    k_end = min(Kv, k_begin + chunk);
-    if (k_begin >= k_end) return;
-  }
-  const float* Ab = d.A + z0 * d.sA0 + z1 * d.sA1;
-  const float* Bb = d.B + z0 * d.sB0 + z1 * d.sB1;
-  const __amdgpu_buffer_rsrc_t ra_src = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, 0x7FFFFFFE, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb_src = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, 0, 0x7FFFFFFE, 0x00020000);
+  if (zero_outside && (row0 + BM > Mv || col0 + BN > Nv)) zero_outside_limits(d, Cb, row0, col0, BM, BN, Mv, Nv, false);
+  float* Cs = Cb;
+  if (d.split_k > 1) Cs += (long)split * d.M * d.ldc;      // split-K: C is the partial matrix P_split of the workspace (ctts_gemm rewrote the descriptor)
+  if (A_KC && d.row_lens && !scheduled_active &&
+      padded_tile_zeroed(d, FT::kPadFillOwnSplit ? Cs : Cb, row0, col0, BM, min(BN, Nv - col0), Mv)) return;
+  int k_begin, k_end;
+  if (!split_k_range(d, Kv, BK, split, k_begin, k_end)) return;
+
+  // ---- operands
   ConvView cv{d.conv_T, d.conv_pad, d.conv_cin};
   ConvView nocv{1, 0, 1};
   constexpr bool CONV_A = CONV && A_KC;
   constexpr bool CONV_B = CONV && !A_KC && !B_KC;
-  using LA = typename BLoaderSel<A_KC, BM, CONV_A, PARTIAL>::type;
-  using LB = typename BLoaderSel<B_KC, BN, CONV_B, PARTIAL>::type;
+  using LA = Loader<FETCH, A_KC, BM, CONV_A>;
+  using LB = Loader<FETCH, B_KC, BN, CONV_B>;
   LA la; LB lb;
-  la.init(d.lda, row0, Mv, CONV_A ? cv : nocv, threadIdx.x);
-  lb.init(d.ldb, col0, Nv, CONV_B ? cv : nocv, threadIdx.x);
+  la.init(d.A + z0 * d.sA0 + z1 * d.sA1, d.lda, row0, Mv, CONV_A ? cv : nocv, threadIdx.x);
+  lb.init(d.B + z0 * d.sB0 + z1 * d.sB1, d.ldb, col0, Nv, CONV_B ? cv : nocv, threadIdx.x);
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, h = lane >> 5;
@@ -669,18 +552,18 @@ __global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_buf_kernel(const ct
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
+  // weight-gradient reductions run over (b,t) rows: K-blocks that lie entirely in the padding of one
+  // sequence contribute exactly zero (dZ is zero there) and are skipped (block-uniform decision)
   constexpr bool KSKIP = !A_KC && !B_KC;
   auto kblock_active = [&](int k0) -> bool {
     if (!KSKIP || !d.row_lens) return true;
-    const int lastk = min(k0 + BK, k_end) - 1;
-    const int b0 = k0 / d.row_T;
-    return !(b0 == lastk / d.row_T && (k0 - b0 * d.row_T) >= d.row_lens[b0] + d.row_halo);
+    return !rows_in_padding(d.row_lens, d.row_T, d.row_halo, k0, min(k0 + BK, k_end) - 1);
   };
   float4 ra[LA::NV], rb[LB::NV];
   bool act_cur = kblock_active(k_begin);
   if (act_cur) {
-    la.load(ra_src, k_begin, k_end, ra);
-    lb.load(rb_src, k_begin, k_end, rb);
+    la.load(k_begin, k_end, ra);
+    lb.load(k_begin, k_end, rb);
     la.store(sA, ra);
     lb.store(sB, rb);
   }
@@ -689,8 +572,8 @@ __global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_buf_kernel(const ct
     const bool has_next = (k0 + BK) < k_end;
     const bool act_next = has_next && kblock_active(k0 + BK);
     if (act_next) {
-      la.load(ra_src, k0 + BK, k_end, ra);
-      lb.load(rb_src, k0 + BK, k_end, rb);
+      la.load(k0 + BK, k_end, ra);
+      lb.load(k0 + BK, k_end, rb);
     }
     if (act_cur) {
 #pragma unroll
@@ -715,7 +598,7 @@ __global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_buf_kernel(const ct
 #endif
       }
     }
-    if (KSKIP && !act_cur && !act_next) continue;
+    if (KSKIP && !act_cur && !act_next) continue;   // nothing staged, nothing to publish: no barrier needed
     __syncthreads();
     if (act_next) {
       la.store(sA, ra);
@@ -724,7 +607,7 @@ __global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_buf_kernel(const ct
     __syncthreads();
     act_cur = act_next;
   }
-  gemm_epilogue_auto<MT, NT>(d, acc, Cb, z, row0, col0, wm0, wn0, l31, h, Mv, Nv);
+  gemm_epilogue_auto<MT, NT>(d, acc, Cs, z, row0, col0, wm0, wn0, l31, h, Mv, Nv);
 }
 
 // ---- fp32 GEMM on the BF16 matrix pipe (NT layout: both operands K-contiguous, conv view on A allowed) --------------------------
@@ -778,49 +661,25 @@ __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(const ctts_gemm_desc d)
   constexpr int BM = 128, BN = 128, MT = 2, NT = 2;
   __shared__ __attribute__((aligned(16))) unsigned char smem[6 * X6_PLANE];       // A hi | mid | lo, B hi | mid | lo
   const int Mv = d.M, Nv = d.N, Kv = d.K;
-  const int tiles_n = d.N / BN, nwg = gridDim.x;
+  const int tiles_n = d.N / BN;
   int wg, tm;
-  if (d.tile_map == reinterpret_cast<const int32_t*>(1)) {
+  if (natural_order(d)) {
     wg = blockIdx.x; tm = wg / tiles_n;
-  } else {          // XCD-contiguous remap + scrambled m order, as the tile kernel without a device-built schedule
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-    const int tiles_m = nwg / tiles_n;
-    tm = wg / tiles_n;
-    const int P = (tiles_m % 37) ? 37 : ((tiles_m % 41) ? 41 : 43);
-    tm = (int)(((long)tm * P) % tiles_m);
+  } else {          // as the tile kernel without a device-built schedule
+    xcd_tile_order(gridDim.x, tiles_n, true, wg, tm);
   }
   const int row0 = tm * BM, col0 = (wg % tiles_n) * BN;
   float* Cb = d.C;
-  if (d.row_lens) {                       // a tile that lies wholly in the padding of one utterance: defined as zero, no operand touched
-    const int last = min(row0 + BM, Mv) - 1;
-    const int b0 = row0 / d.row_T, b1 = last / d.row_T;
-    if (b0 == b1 && (row0 - b0 * d.row_T) >= d.row_lens[b0] + d.row_halo) {
-      const int nrows = last - row0 + 1;
-      for (int e = threadIdx.x; e < nrows * BN; e += 256) {
-        const int r = e / BN, c = e - r * BN;
-        Cb[(long)(row0 + r) * d.ldc + col0 + c] = 0.f;
-        if (d.Z && !d.epi_bwd) d.Z[(long)(row0 + r) * d.ldz + col0 + c] = 0.f;
-      }
-      return;
-    }
-  }
+  if (d.row_lens && padded_tile_zeroed(d, Cb, row0, col0, BM, BN, Mv)) return;
   // the zero rule has 64-row granularity in the other kernels (and in the tile schedules built for them): when only the UPPER 64 rows of
   // this tile lie wholly in padding, the two waves that own them write zeros instead of their epilogue
-  bool pad_hi = false;
-  if (d.row_lens && row0 + 64 < Mv) {
-    const int first = row0 + 64, last = min(row0 + BM, Mv) - 1;
-    const int b0 = first / d.row_T;
-    pad_hi = b0 == last / d.row_T && (first - b0 * d.row_T) >= d.row_lens[b0] + d.row_halo;
-  }
-  const __amdgpu_buffer_rsrc_t ra_src = __builtin_amdgcn_make_buffer_rsrc((void*)d.A, 0, 0x7FFFFFFE, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb_src = __builtin_amdgcn_make_buffer_rsrc((void*)d.B, 0, 0x7FFFFFFE, 0x00020000);
+  const bool pad_hi = d.row_lens && row0 + 64 < Mv && rows_in_padding(d.row_lens, d.row_T, d.row_halo, row0 + 64, min(row0 + BM, Mv) - 1);
   ConvView cv{d.conv_T, d.conv_pad, d.conv_cin};
   ConvView nocv{1, 0, 1};
-  BLoaderKC<BM, CONV, false> la;
-  BLoaderKC<BN, false, false> lb;
-  la.init(d.lda, row0, Mv, CONV ? cv : nocv, threadIdx.x);
-  lb.init(d.ldb, col0, Nv, nocv, threadIdx.x);
+  Loader<Fetch::Buffer, true, BM, CONV> la;
+  Loader<Fetch::Buffer, true, BN, false> lb;
+  la.init(d.A, d.lda, row0, Mv, CONV ? cv : nocv, threadIdx.x);
+  lb.init(d.B, d.ldb, col0, Nv, nocv, threadIdx.x);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, h = lane >> 5;
   const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
@@ -841,16 +700,16 @@ __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(const ctts_gemm_desc d)
   const unsigned char* fr_a = smem + (wm0 + l31) * X6_PROW;
   const unsigned char* fr_b = smem + 3 * X6_PLANE + (wn0 + l31) * X6_PROW;
   const int fc0 = x6_chunk(l31, h) * 16, fc1 = x6_chunk(l31, 2 + h) * 16;      // byte offsets of the fragment chunk for ks = 0, 1
-  la.load(ra_src, 0, Kv, ra);
-  lb.load(rb_src, 0, Kv, rb);
+  la.load(0, Kv, ra);
+  lb.load(0, Kv, rb);
 #pragma unroll
   for (int i = 0; i < 4; ++i) { x6_split_store(ra[i], st_a + 32 * i * X6_PROW); x6_split_store(rb[i], st_b + 32 * i * X6_PROW); }
   __syncthreads();
   for (int k0 = 0; k0 < Kv; k0 += BK) {
     {                                      // unconditional (the last block is fetched again): keeps the staging registers in registers
       const int kn = k0 + BK < Kv ? k0 + BK : k0;
-      la.load(ra_src, kn, Kv, ra);
-      lb.load(rb_src, kn, Kv, rb);
+      la.load(kn, Kv, ra);
+      lb.load(kn, Kv, rb);
     }
     // all fragments of the K-block first (one exposed LDS round trip per block instead of one per 16-deep step), then the 48 MFMAs
     ctts_u32x4 fa[2][MT][3], fb[2][NT][3];
@@ -906,28 +765,16 @@ __global__ __launch_bounds__(256, 2) void gemm_x6tn_kernel(const ctts_gemm_desc 
   constexpr int BM = 128, BN = 128, MT = 2, NT = 2;
   __shared__ __attribute__((aligned(16))) unsigned char smem[6 * X6_PLANE];
   const int Mv = d.M, Nv = d.N, Kv = d.K;
-  const int tiles_n = d.N / BN, nwg = gridDim.x, split = blockIdx.y;
+  const int tiles_n = d.N / BN, split = blockIdx.y;
   int wg, tm;
-  {
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-    tm = wg / tiles_n;
-  }
+  xcd_tile_order(gridDim.x, tiles_n, false, wg, tm);
   const int row0 = tm * BM, col0 = (wg % tiles_n) * BN;
   float* Cb = d.C;
   if (d.split_k > 1) Cb += (long)split * d.M * d.ldc;        // partial matrix P_split (ctts_gemm rewrote the descriptor)
-  int k_begin = 0, k_end = Kv;
-  if (d.split_k > 1) {
-    const int chunk = ((Kv + d.split_k - 1) / d.split_k + BK - 1) / BK * BK;
-    k_begin = split * chunk;
-    k_end = min(Kv, k_begin + chunk);
-    if (k_begin >= k_end) return;
-  }
+  int k_begin, k_end;
+  if (!split_k_range(d, Kv, BK, split, k_begin, k_end)) return;
   auto kblock_active = [&](int k0) -> bool {
-    if (!d.row_lens) return true;
-    const int lastk = min(k0 + BK, k_end) - 1;
-    const int b0 = k0 / d.row_T;
-    return !(b0 == lastk / d.row_T && (k0 - b0 * d.row_T) >= d.row_lens[b0] + d.row_halo);
+    return !d.row_lens || !rows_in_padding(d.row_lens, d.row_T, d.row_halo, k0, min(k0 + BK, k_end) - 1);
   };
   auto next_active = [&](int k0) -> int { while (k0 < k_end && !kblock_active(k0)) k0 += BK; return k0; };
   const __amdgpu_buffer_rsrc_t ra_src = __builtin_amdgcn_make_buffer_rsrc((void*)d.A, 0, 0x7FFFFFFE, 0x00020000);
@@ -1054,39 +901,18 @@ __global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_buf_k2_kernel(const
   if (row0 >= Mv || col0 >= Nv) return;
   float* Cb = d.C + z0 * d.sC0 + z1 * d.sC1;
   if (d.split_k > 1) Cb += (long)split * d.M * d.ldc;      // split-K: C is the partial matrix P_split of the workspace
-  if (A_KC && d.row_lens) {
-    const int last = min(row0 + BM, Mv) - 1;
-    const int b0 = row0 / d.row_T, b1 = last / d.row_T;
-    if (b0 == b1 && (row0 - b0 * d.row_T) >= d.row_lens[b0] + d.row_halo) {
-      const int ncols = min(BN, Nv - col0), nrows = last - row0 + 1;
-      for (int e = threadIdx.x; e < nrows * ncols; e += 256) {
-        const int r = e / ncols, c = e - r * ncols;
-        Cb[(long)(row0 + r) * d.ldc + col0 + c] = 0.f;
-        if (d.Z && !d.epi_bwd) d.Z[(long)(row0 + r) * d.ldz + col0 + c] = 0.f;
-      }
-      return;
-    }
-  }
-  int k_begin = 0, k_end = Kv;
-  if (d.split_k > 1) {
-    int chunk = ((Kv + d.split_k - 1) / d.split_k + 2 * BK - 1) / (2 * BK) * (2 * BK);
-    k_begin = split * chunk;
-    k_end = min(Kv, k_begin + chunk);
-    if (k_begin >= k_end) return;
-  }
-  const float* Ab = d.A + z0 * d.sA0 + z1 * d.sA1;
-  const float* Bb = d.B + z0 * d.sB0 + z1 * d.sB1;
-  const __amdgpu_buffer_rsrc_t ra_src = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, 0x7FFFFFFE, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb_src = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, 0, 0x7FFFFFFE, 0x00020000);
+  if (A_KC && d.row_lens && padded_tile_zeroed(d, Cb, row0, col0, BM, min(BN, Nv - col0), Mv)) return;
+  int k_begin, k_end;
+  if (!split_k_range(d, Kv, 2 * BK, split, k_begin, k_end)) return;
   ConvView cv{d.conv_T, d.conv_pad, d.conv_cin};
   ConvView nocv{1, 0, 1};
   constexpr bool CONV_A = CONV && A_KC;
   constexpr bool CONV_B = CONV && !A_KC && !B_KC;
-  using LA = typename BLoaderSel<A_KC, BM, CONV_A, false>::type;
-  using LB = typename BLoaderSel<B_KC, BN, CONV_B, false>::type;
+  using LA = Loader<Fetch::Buffer, A_KC, BM, CONV_A>;
+  using LB = Loader<Fetch::Buffer, B_KC, BN, CONV_B>;
   LA la; LB lb;
-  la.init(d.lda, row0, Mv, CONV_A ? cv : nocv, threadIdx.x);
-  lb.init(d.ldb, col0, Nv, CONV_B ? cv : nocv, threadIdx.x);
+  la.init(d.A + z0 * d.sA0 + z1 * d.sA1, d.lda, row0, Mv, CONV_A ? cv : nocv, threadIdx.x);
+  lb.init(d.B + z0 * d.sB0 + z1 * d.sB1, d.ldb, col0, Nv, CONV_B ? cv : nocv, threadIdx.x);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, h = lane >> 5;
   const int grp = wave >> 1, wn0 = (wave & 1) * 32;
@@ -1097,8 +923,8 @@ __global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_buf_k2_kernel(const
   for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
   float4 ra[2][LA::NV], rb[2][LB::NV];
   auto load_round = [&](int k0) {                       // both 32-deep K-blocks of the round (the second may lie beyond k_end: zeros)
-    la.load(ra_src, k0, k_end, ra[0]);      lb.load(rb_src, k0, k_end, rb[0]);
-    la.load(ra_src, k0 + BK, k_end, ra[1]); lb.load(rb_src, k0 + BK, k_end, rb[1]);
+    la.load(k0, k_end, ra[0]);      lb.load(k0, k_end, rb[0]);
+    la.load(k0 + BK, k_end, ra[1]); lb.load(k0 + BK, k_end, rb[1]);
   };
   auto store_round = [&]() {
     la.store(smem, ra[0]);                  lb.store(smem + A_SZ, rb[0]);
@@ -1161,34 +987,24 @@ int for_layout(const ctts_gemm_desc& d, F f) {
   return -1;
 }
 
-int dispatch_buf_k2(const ctts_gemm_desc& d, hipStream_t st) {
-  return for_layout<true>(d, [&](auto a, auto b, auto c) { return launch_buf_k2<a(), b(), c()>(d, st); });
-}
-
-template <int BM, int BN, bool A_KC, bool B_KC, bool CONV>
-int launch_buf(const ctts_gemm_desc& d, hipStream_t st) {
-  const int tiles = ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
-  const int nz = d.nb0 * d.nb1, ny = d.split_k > 1 ? d.split_k : 1;
-  if (d.lens && (d.lim_m || d.lim_n || d.lim_k)) {
-    if constexpr (!CONV) {
-      hipLaunchKernelGGL((gemm_buf_kernel<BM, BN, A_KC, B_KC, false, true>), dim3(tiles, ny, nz), dim3(256), 0, st, d);
-      CTTS_CHECK_LAUNCH("ctts_gemm(buf,partial)");
-      return 0;
-    } else {
-      ctts_set_error("ctts_gemm: per-batch length limits together with a conv view are not supported");
-      return -1;
+// One launch of the tile kernel.  Buffer fetch with per-batch length limits in force goes to the partial variant (no conv instantiations).
+template <int BM, int BN, bool A_KC, bool B_KC, bool CONV, Fetch FETCH>
+int launch_tile(const ctts_gemm_desc& d, hipStream_t st) {
+  if constexpr (FETCH == Fetch::Buffer) {
+    if (d.lens && (d.lim_m || d.lim_n || d.lim_k)) {
+      if constexpr (!CONV) {
+        return launch_tile<BM, BN, A_KC, B_KC, false, Fetch::BufferPartial>(d, st);
+      } else {
+        ctts_set_error("ctts_gemm: per-batch length limits together with a conv view are not supported");
+        return -1;
+      }
     }
   }
-  hipLaunchKernelGGL((gemm_buf_kernel<BM, BN, A_KC, B_KC, CONV, false>), dim3(tiles, ny, nz), dim3(256), 0, st, d);
-  CTTS_CHECK_LAUNCH("ctts_gemm(buf)");
+  const int tiles = ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
+  const int nz = d.nb0 * d.nb1, ny = d.split_k > 1 ? d.split_k : 1;
+  hipLaunchKernelGGL((gemm_tile_kernel<BM, BN, A_KC, B_KC, CONV, FETCH>), dim3(tiles, ny, nz), dim3(256), 0, st, d);
+  CTTS_CHECK_LAUNCH(FETCH == Fetch::BufferPartial ? "ctts_gemm(buf,partial)" : FETCH == Fetch::Buffer ? "ctts_gemm(buf)" : "ctts_gemm");
   return 0;
-}
-
-// 128 x 32 tiles (4 x 1 waves) for outputs at most 32 columns wide: with 64 x 64 tiles half of every workgroup's MFMAs would multiply
-// zero columns.  The three products of the conformer's attention backward that consume dS ([T, 32] = [T, T] x [T, 32] per (b, h),
-// ctts_relmha_bwd) are the users.  No conv views.
-int dispatch_buf_narrow(const ctts_gemm_desc& d, hipStream_t st) {
-  return for_layout<false>(d, [&](auto a, auto b, auto c) { return launch_buf<128, 32, a(), b(), c()>(d, st); });
 }
 
 // buffer loaders need: no per-batch length limits and every operand element within 2 GiB of its (batch) base
@@ -1211,18 +1027,11 @@ bool vec_ok(const ctts_gemm_desc& d) {
   return strides && chunks_ok(d) && al16(d.A) && al16(d.B);
 }
 
-}  // namespace
-
-namespace {
 // one wave: stable partition of the m-tiles into active (first) and inactive, count in map[0]
 __global__ __launch_bounds__(64) void row_tile_map_kernel(const int32_t* __restrict__ row_lens, int row_T, int row_halo, int M,
                                                             int32_t* __restrict__ map) {
   const int tiles = (M + 63) / 64, lane = threadIdx.x;
-  auto inactive = [&](int tm) -> bool {
-    const int row0 = tm * 64, last = min(row0 + 64, M) - 1;
-    const int b0 = row0 / row_T, b1 = last / row_T;
-    return b0 == b1 && (row0 - b0 * row_T) >= row_lens[b0] + row_halo;
-  };
+  auto inactive = [&](int tm) -> bool { return rows_in_padding(row_lens, row_T, row_halo, tm * 64, min(tm * 64 + 64, M) - 1); };
   int n_act = 0;
   for (int base = 0; base < tiles; base += 64) {
     const int tm = base + lane;
@@ -1241,27 +1050,16 @@ __global__ __launch_bounds__(64) void row_tile_map_kernel(const int32_t* __restr
   }
   if (lane == 0) map[0] = n_act;
 }
-}  // namespace
 
-namespace {
 // Second launch of a split-K GEMM: C[m, n] += alpha * (P_0 + P_1 + ... )[m, n] in split order (fixed: bit-reproducible), for the rows /
 // columns / batches the GEMM kernels computed - per-batch length limits, tiles of padded rows (zero-filled by the GEMM, skipped here) and
 // splits whose K range was empty (never written) follow the kernels' own predicates.  One thread per 4 columns, all splits' loads in flight.
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ctts_gemm_desc d, int BM, int kround) {
   const int z = blockIdx.z, z0 = z / d.nb1, z1 = z - z0 * d.nb1;
-  int Mv = d.M, Nv = d.N, Kv = d.K;
-  if (d.lens) {
-    const int L = d.lens[z0];
-    if (d.lim_m) Mv = min(Mv, L);
-    if (d.lim_n) Nv = min(Nv, L);
-    if (d.lim_k) Kv = min(Kv, L);
-  }
+  int Mv, Nv, Kv;
+  batch_limits(d, z0, true, Mv, Nv, Kv);
   const bool ow = d.split_overwrite != 0;      // C = alpha * sum (and ZERO outside the limits / in padded tiles) instead of C += : no pre-zeroed C
-  int nact = 0;
-  if (Kv > 0) {
-    const int chunk = ((Kv + d.split_k - 1) / d.split_k + kround - 1) / kround * kround;
-    nact = (Kv + chunk - 1) / chunk;
-  }
+  const int nact = Kv > 0 ? gemm_split_range(Kv, d.split_k, kround, 0).nonempty : 0;
   if (nact == 0 && !ow) return;
   const long ldp = gemm_partial_ld(d.N);
   const int n4 = (int)(ldp >> 2);
@@ -1270,9 +1068,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ctts_gemm_desc
   if (m >= d.M || n >= d.N) return;
   bool live = m < Mv && n < Nv && nact > 0;
   if (live && d.a_kc && d.row_lens) {          // the GEMM wrote no partials for whole tiles of padded rows (their result is defined as zero)
-    const int row0 = m / BM * BM, last = min(row0 + BM, Mv) - 1;
-    const int b0 = row0 / d.row_T, b1 = last / d.row_T;
-    if (b0 == b1 && (row0 - b0 * d.row_T) >= d.row_lens[b0] + d.row_halo) live = false;
+    const int row0 = m / BM * BM;
+    if (rows_in_padding(d.row_lens, d.row_T, d.row_halo, row0, min(row0 + BM, Mv) - 1)) live = false;
   }
   if (!live && !ow) return;
   float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1519,16 +1316,19 @@ extern "C" int ctts_gemm(const ctts_gemm_desc* dp, void* stream) {
     case CTTS_GEMM_WEIGHT_STATIONARY: return ctts_gemm_ws_launch(d, r.ws, r.grid, st);
     case CTTS_GEMM_X6: return x6_launch(d, st);
     case CTTS_GEMM_STREAM_K: return ctts_gemm_sk_launch(d, r.sk, r.grid, st);
-    case CTTS_GEMM_SCALAR64: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch<64, 64, a(), b(), c(), false>(t, st); }); break;
+    case CTTS_GEMM_SCALAR64: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch_tile<64, 64, a(), b(), c(), Fetch::Scalar>(t, st); }); break;
 #ifndef CTTS_NO_BUF
-    case CTTS_GEMM_BUF128: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch_buf<128, 128, a(), b(), c()>(t, st); }); break;
-    case CTTS_GEMM_BUF_K2: rc = dispatch_buf_k2(t, st); break;
-    case CTTS_GEMM_BUF_NARROW: rc = dispatch_buf_narrow(t, st); break;
-    case CTTS_GEMM_BUF64: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch_buf<64, 64, a(), b(), c()>(t, st); }); break;
+    case CTTS_GEMM_BUF128: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch_tile<128, 128, a(), b(), c(), Fetch::Buffer>(t, st); }); break;
+    case CTTS_GEMM_BUF_K2: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch_buf_k2<a(), b(), c()>(t, st); }); break;
+    // 128 x 32 tiles (4 x 1 waves) for outputs at most 32 columns wide: with 64 x 64 tiles half of every workgroup's MFMAs would multiply
+    // zero columns.  The three products of the conformer's attention backward that consume dS ([T, 32] = [T, T] x [T, 32] per (b, h),
+    // ctts_relmha_bwd) are the users.  No conv views.
+    case CTTS_GEMM_BUF_NARROW: rc = for_layout<false>(t, [&](auto a, auto b, auto c) { return launch_tile<128, 32, a(), b(), c(), Fetch::Buffer>(t, st); }); break;
+    case CTTS_GEMM_BUF64: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch_tile<64, 64, a(), b(), c(), Fetch::Buffer>(t, st); }); break;
 #endif
-    case CTTS_GEMM_VEC128: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch<128, 128, a(), b(), c(), true>(t, st); }); break;
+    case CTTS_GEMM_VEC128: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch_tile<128, 128, a(), b(), c(), Fetch::Vec>(t, st); }); break;
     case CTTS_GEMM_X6TN: rc = x6tn_launch(t, st); break;
-    default: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch<64, 64, a(), b(), c(), true>(t, st); }); break;
+    default: rc = for_layout<true>(t, [&](auto a, auto b, auto c) { return launch_tile<64, 64, a(), b(), c(), Fetch::Vec>(t, st); }); break;
   }
   if (rc != 0 || !split || d.split_out) return rc;
   return splitk_reduce(d_user, r.info.tile_m, r.info.k_granule, st);
@@ -1575,8 +1375,7 @@ extern "C" int ctts_gemm_split_plan(const ctts_gemm_desc* dp, int32_t* count, in
   gemm_route(d, r, true);
   if (r.info.kind < CTTS_GEMM_X6TN || !r.split_fits) return 0;
   if (d.nb0 * d.nb1 != 1 || d.lens || d.K <= 0 || (d.a_kc && d.row_lens)) return 0;
-  const int chunk = ((d.K + r.info.split_k - 1) / r.info.split_k + r.info.k_granule - 1) / r.info.k_granule * r.info.k_granule;
-  if (count) *count = (d.K + chunk - 1) / chunk;
+  if (count) *count = gemm_split_range(d.K, r.info.split_k, r.info.k_granule, 0).nonempty;
   if (stride) *stride = (long)d.M * gemm_partial_ld(d.N);
   return 1;
 }

@@ -254,6 +254,15 @@ __device__ __forceinline__ void gemm_accumulate_lean(const ctts_gemm_desc& d, co
 // EVERY launch, and a 25 us serial gather at the tail of every 31-way split).
 // P_s of (batch z, split s): the partial matrices live in the slab area of the workspace, [z][s][M][ldp], ldp = N rounded up to 4
 __device__ __host__ __forceinline__ long gemm_partial_ld(int N) { return (long)((N + 3) / 4) * 4; }
+// The K range of split `split` of split_k: [0, Kv) is cut into equal chunks, rounded up to the kernel's K granule; trailing splits may
+// be empty (k_begin >= k_end: their partial matrix is never written).  nonempty: how many splits are not - the kernels, the reduce
+// launch and the host's split plan must agree on it, or the reduce reads partial matrices that no kernel wrote.
+struct GemmSplitRange { int k_begin, k_end, nonempty; };
+__device__ __host__ __forceinline__ GemmSplitRange gemm_split_range(int Kv, int split_k, int granule, int split) {
+  const int chunk = ((Kv + split_k - 1) / split_k + granule - 1) / granule * granule;
+  const int k_begin = split * chunk, k_stop = k_begin + chunk;
+  return GemmSplitRange{k_begin, k_stop < Kv ? k_stop : Kv, Kv > 0 ? (Kv + chunk - 1) / chunk : 0};
+}
 __device__ __forceinline__ float* gemm_partial_base(const ctts_gemm_desc& d, int z, int split) {
   float* P = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(d.sk_ws) + CTTS_WS_SLABS);
   return P + ((long)z * d.split_k + split) * (long)d.M * gemm_partial_ld(d.N);

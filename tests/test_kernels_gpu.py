@@ -1449,7 +1449,8 @@ _ROUTE_CASES = [
 @pytest.mark.parametrize("kind,layout,M,N,Kd,make,kw,bound", _ROUTE_CASES, ids=[c[0] for c in _ROUTE_CASES])
 def test_every_route_kind_names_the_kernel_that_runs_the_launch(kind, layout, M, N, Kd, make, kw, bound):
     """K.gemm_route names `kind` for the descriptor, and the launch of the same descriptor computes the product: binds every route kind
-    that a small launch reaches to its launcher (the vec kinds need an operand beyond 2 GiB, buf128 a tuning knob: tests/test_gemm_route_cpu.py)."""
+    that a small launch reaches to its launcher (the vec kinds need an operand beyond 2 GiB: the test below; buf128 a tuning knob:
+    tests/test_gemm_route_cpu.py)."""
     g = torch.Generator().manual_seed(41)
     A, Bm = make(M, N, Kd, g)
     ref = A.double() @ Bm.double().t()
@@ -1472,3 +1473,37 @@ def test_every_route_kind_names_the_kernel_that_runs_the_launch(kind, layout, M,
     if kind in ("x6", "x6tn"):
         assert scale < 2 ** 24
     assert err <= bound(scale), (err, bound(scale))
+
+
+@pytest.mark.parametrize("kind,M,N,Kd,kw", [("vec64", 70, 50, 32, {}), ("vec128", 2048, 2048, 64, dict(bf16_split=0, use_sk=False))],
+                         ids=["vec64", "vec128"])
+def test_pointer_vec_route_kinds_run_an_operand_beyond_the_buffer_window(kind, M, N, Kd, kw):
+    """The 16-byte pointer-load tile kernels take aligned operands that a 2 GiB buffer window does not cover: A is a view with the
+    smallest leading dimension (a multiple of 4) for which (M * lda + K) * 4 >= 0x7FFF0000 - about 2.2 GB of uninitialised storage of
+    which only the M rows used are written.  Route kind first, then the product against float64 under test_gemm_nt's bound; printed:
+    whether the result is bit-equal to the buffer kernel's on a compact copy of the same operands."""
+    g = torch.Generator().manual_seed(43)
+    A, Bm = _route_unit(M, N, Kd, g)
+    ref = A.double() @ Bm.double().t()
+    lda = -(-(0x7FFF0000 // 4 - Kd) // M)            # ceil((0x7FFF0000 / 4 - K) / M) ...
+    lda += -lda % 4                                   # ... rounded up to a multiple of 4
+    assert (M * lda + Kd) * 4 >= 0x7FFF0000 > (M * (lda - 4) + Kd) * 4
+    store = torch.empty((M - 1) * lda + Kd, device=DEV)
+    dA = store.as_strided((M, Kd), (lda, 1))
+    dA.copy_(A)
+    dB, out = Bm.to(DEV), torch.full((M, N), float("nan"), device=DEV)
+    args = (store, dB, out, M, N, Kd, lda, Kd, N, True, True)
+    route = K.gemm_route(*args, **kw)
+    assert route.kind == kind, route
+    K.gemm(*args, **kw)
+    compact, out_c = dA.contiguous(), torch.full((M, N), float("nan"), device=DEV)
+    args_c = (compact, dB, out_c, M, N, Kd, Kd, Kd, N, True, True)
+    kind_c = K.gemm_route(*args_c, **kw).kind
+    K.gemm(*args_c, **kw)
+    torch.cuda.synchronize()
+    del store, dA
+    err, scale = float((out.double().cpu() - ref).abs().max()), float(ref.abs().max())
+    bound = 2e-6 * max(1, Kd / 16) * max(1.0, scale)
+    print(f"{kind}: max |err| vs fp64 {err:.3e} (|ref| max {scale:.3e}, bound {bound:.3e}); bit-equal to {kind_c} on a compact copy: "
+          f"{torch.equal(out, out_c)}")
+    assert err <= bound, (err, bound)
