@@ -19,7 +19,7 @@
 //     first half's MFMAs are issued; at the barrier every wave has finished reading this stage (so the DMA of block i+2 may overwrite it)
 //     and block i+1 has landed (so its first-half fragments are read while the second half's MFMAs run).  Neither the DMA latency nor
 //     the LDS read latency is exposed - only the barrier skew;
-//   * persistent grid with the even (tile, K-block) partition and the fixed-order slab hand-off of gemm_sk.hip (sk_plan.h): deterministic;
+//   * persistent grid with the even (tile, K-block) partition and the fixed-order slab hand-off of all stream-K kernels (sk_plan.h, sk_handoff.h): deterministic;
 //   * conv view on A (implicit im2col, K walked channel-block-major so that consecutive K-blocks re-read the same lines shifted by a row);
 //   * ragged (b, t) rows: the schedule of the ACTIVE 128-row tiles is built by every workgroup itself from row_lens (prefix sums in LDS;
 //     row_T % 128 == 0), wholly padded tiles are zero-filled, and - the zero rule has 64-row granularity in the other kernels - the waves
@@ -81,11 +81,7 @@ __device__ __forceinline__ void pl_epilogue(const ctts_gemm_desc& d, const float
 #define PL_SLAB_BATCH 8
 #endif
 
-struct PlFrag { pl_u32x4 a[2][3], b[2][3]; };      // one 16-deep k-step: [MFMA row / column tile][plane]
-
-// TERMS = 6: fp32 products from the six cross terms of the three-way split (bf16_split 1 / 2).  TERMS = 1: the "amp" arithmetic
-// (bf16_split 3 / 4; reference train.py:59,104 `amp.autocast`): operands ROUNDED to bf16 - only the hi pieces are moved and multiplied -
-// fp32 accumulate: one MFMA term, a third of the operand traffic.  Never the default, reported separately.
+// TERMS: 6 = the six cross terms of the three-way split; 1 = the "amp" arithmetic, hi pieces only (pl_mma_terms, gemm_pl_common.h)
 template <bool CONV, int TERMS>
 __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d, const PlArgs p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * PL_STAGE];
@@ -159,13 +155,12 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
   const int cin = d.conv_cin > 0 ? d.conv_cin : 32;
   const int T = d.conv_T > 0 ? d.conv_T : 1;
   // plane set: row stride 3 * ld bf16 = 6 * ld bytes; K-block kb of a row at + kb * 192 bytes, piece q at + q * 64 bytes
-  const pl_i32x4 ra_src = pl_make_rsrc(d.A_planes - (CONV ? (long)d.conv_pad * d.lda * 3 : 0));
-  const pl_i32x4 rb_src = pl_make_rsrc(d.B_planes);
+  const sk_i32x4 ra_src = sk_make_rsrc(d.A_planes - (CONV ? (long)d.conv_pad * d.lda * 3 : 0));
+  const sk_i32x4 rb_src = sk_make_rsrc(d.B_planes);
   const unsigned lda2 = (unsigned)(d.lda * 6), ldb2 = (unsigned)(d.ldb * 6);
   const unsigned smem_addr = (unsigned)reinterpret_cast<uintptr_t>(smem);
   unsigned* flags = p.ws;
-  float* slabs = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(p.ws) + CTTS_WS_SLABS);
-  const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc((void*)slabs, 0, 0x7FFFFFFE, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_src = sk_slab_rsrc(p.ws);
 
   // ---- (schedule slot, n-tile) -> rows / columns; pad_hi: the upper 64 rows of the tile lie wholly in one utterance's padding
   auto decode = [&](const SkPiece& pc, int& row0, int& col0, bool& pad_hi) {
@@ -221,11 +216,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
     const unsigned sB = smem_addr + (unsigned)(stage * PL_STAGE + 3 * PL_A_PLANE + wave * 2048);
     // the three pieces of a row group back to back: they share cache lines
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) pl_dma16(ra_src, sA + q * PL_A_PLANE, vA, soffA + q * 64);
+    for (int q = 0; q < NQ; ++q) sk_dma16(ra_src, sA + q * PL_A_PLANE, vA, soffA + q * 64);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int q = 0; q < NQ; ++q) pl_dma16(rb_src, sB + q * PL_B_PLANE + j * 1024, voffB[j], soffB + q * 64);
+      for (int q = 0; q < NQ; ++q) sk_dma16(rb_src, sB + q * PL_B_PLANE + j * 1024, voffB[j], soffB + q * 64);
   };
   auto loader_advance = [&]() {
     ++lkb;
@@ -249,42 +244,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int q = 0; q < NQ; ++q) f.a[i][q] = *reinterpret_cast<const pl_u32x4*>(pa + q * PL_A_PLANE + i * 32 * PL_ROW);
+      for (int q = 0; q < NQ; ++q) f.a[i][q] = *reinterpret_cast<const sk_u32x4*>(pa + q * PL_A_PLANE + i * 32 * PL_ROW);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int q = 0; q < NQ; ++q) f.b[j][q] = *reinterpret_cast<const pl_u32x4*>(pb + q * PL_B_PLANE + j * 32 * PL_ROW);
+      for (int q = 0; q < NQ; ++q) f.b[j][q] = *reinterpret_cast<const sk_u32x4*>(pb + q * PL_B_PLANE + j * 32 * PL_ROW);
   };
   floatx16 acc[2][2];
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  };
-  // terms [t0, t1) of the six-term product of one k-step; term-major: consecutive MFMAs hit different accumulators; smallest terms first
-  auto mma_terms = [&](const PlFrag& f, int t0, int t1) {
-    if constexpr (TERMS == 1) {          // hi x hi only
-      if (t0 <= 5 && 5 < t1) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = pl_mma(f.a[i][0], f.b[j][0], acc[i][j]);
-      }
-      return;
-    }
-#pragma unroll
-    for (int t = 0; t < 6; ++t) {
-      constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-      if (t < t0 || t >= t1) continue;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = pl_mma(f.a[i][PA[t]], f.b[j][PB[t]], acc[i][j]);
-    }
-  };
 
   // ---- prologue: blocks 0 and 1 in flight, first-half fragments of block 0 in registers
   loader_set_piece();
@@ -299,7 +265,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
   sk_next_piece(cu, rg.lo, nkb, cp);
   int ckb = cp.kb_lo;
   int remaining = rg.hi - rg.lo;              // K-blocks this workgroup still has to compute (the current one included)
-  zero_acc();
+  pl_zero_acc(acc);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   // The K loop exists twice - once per wave group, chosen ONCE by a wave-uniform branch: the same work in two instruction orders (see the
   // comment in the loop).  Both copies execute the same sequence of barriers.
@@ -326,7 +292,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
     // same loop without DMA: 314 us with bursts, 253 us without any reads).  An idle upper wave (SKEW, half-padded tile) skips both.
     if (do_mma) {
       read_frag(stage, 1, f1);
-      mma_terms(f0, 0, 6);
+      pl_mma_terms<TERMS>(acc, f0, 0, 6);
       if constexpr (TERMS == 1) { PL_INTERLEAVE_4x1(); } else { PL_INTERLEAVE_12(); }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -346,7 +312,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
     }
     if (do_mma) {
       read_frag(stage ^ 1, 0, f0);
-      mma_terms(f1, 0, 6);
+      pl_mma_terms<TERMS>(acc, f1, 0, 6);
       if constexpr (TERMS == 1) { PL_INTERLEAVE_4x1(); } else { PL_INTERLEAVE_12(); }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -360,19 +326,15 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
     if (ckb < cp.kb_hi) continue;
 
     // ---------------- the piece is complete
-    // Everything below runs once per piece and must not cost the K loop registers.  (1) Its lane / wave constants are laundered through an
-    // empty asm so that loop-invariant code motion cannot hoist the epilogues' lane offsets in front of the K loop.  (2) The descriptor
-    // fields only the epilogue needs (C, Z, bias, strides, dropout, ...) are read HERE from the kernel-argument segment (`d` is the first
-    // kernel argument: offset 0) through a laundered pointer: s_load at the point of use instead of ~60 SGPRs that stay live across the
-    // K loop - hipcc preloads a by-value struct argument and then spills it to VGPR lanes (560 SGPR spills, 27 VGPR spills and scratch
-    // reloads in front of every DMA issue in the first build of this kernel).
-    int e_l31 = l31, e_h = h, e_wm0 = wm0, e_wn0 = wn0;
-    unsigned long long kargs = (unsigned long long)(const void*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+v"(e_l31), "+v"(e_h), "+s"(e_wm0), "+s"(e_wn0), "+s"(kargs));
-    const ctts_gemm_desc& dc = *(const ctts_gemm_desc*)(const __attribute__((address_space(4))) ctts_gemm_desc*)kargs;
+    PL_PIECE_COMPLETE();          // -> dc, e_l31, e_h, e_wm0, e_wn0: nothing below costs the K loop registers
     const int Mv = dc.M, Nv = dc.N;
     int row0, col0; bool pad_hi;
     decode(cp, row0, col0, pad_hi);
+    // The hand-off below is sk_slab_publish<2, 2, 8> / sk_slab_collect<2, 2, 8, PL_SLAB_BATCH> of sk_handoff.h WRITTEN OUT: the protocol is
+    // defined there (gemm_sk.hip and gemm_plw.hip call it) and this copy must follow it word for word.  Calling the helpers here gives the
+    // same K loops and the same hand-off instructions, but the launches with many cut tiles measured 0.3 - 1 % slower, outside the
+    // spread of repeated runs (FFN conv data gradient 267.7 -> 270.2 us, encoder-sized 80.3 -> 81.6 us;
+    // profiles/streamk_handoff_refactor_isa.md) - cause not found, so this kernel keeps its text.
     if (cp.kb_hi < nkb) {
       // contribution: slab (write-through stores) + flag
       const unsigned base = (unsigned)blockIdx.x * (PL_SLAB * 4) + (unsigned)(wave * (PL_SLAB / 8) + lane * 4) * 4u;
@@ -382,14 +344,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            pl_u32x4 v;
+            sk_u32x4 v;
             v.x = __float_as_uint(acc[i][j][4 * q + 0]); v.y = __float_as_uint(acc[i][j][4 * q + 1]);
             v.z = __float_as_uint(acc[i][j][4 * q + 2]); v.w = __float_as_uint(acc[i][j][4 * q + 3]);
             __builtin_amdgcn_raw_buffer_store_b128(v, rs_src, base + (unsigned)(((i * 2 + j) * 4 + q) * 1024), 0, 16);      // aux 16 = sc1
           }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == 0) __hip_atomic_store((pl_gu32*)(flags + blockIdx.x), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (tid == 0) __hip_atomic_store((sk_gu32*)(flags + blockIdx.x), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else {
       if (cp.kb_lo > 0) {
         // owner of a cut tile: add the slabs of the workgroups below, nearest first, until the tile's unit 0 is covered
@@ -403,14 +365,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
           const int src = jj * 8 + xcd;
           if (tid == 0) {
             unsigned spins = 0;
-            while (__hip_atomic_load((pl_gu32*)(flags + src), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 1u) {
+            while (__hip_atomic_load((sk_gu32*)(flags + src), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 1u) {
               __builtin_amdgcn_s_sleep(8);
               if (++spins > (1u << 24)) {
-                __hip_atomic_store((pl_gu32*)(flags + PL_MAX_WG), 1u + (unsigned)src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store((sk_gu32*)(flags + SK_MAX_WG), 1u + (unsigned)src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
               }
             }
-            __hip_atomic_store((pl_gu32*)(flags + src), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store((sk_gu32*)(flags + src), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
           }
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -421,7 +383,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
           // cut tile.  (All 16 at once cost this kernel 59 - 72 spilled VGPRs with reloads inside the K loop; gemm_plw.hip affords it.)
 #pragma unroll
           for (int g = 0; g < 16 / PL_SLAB_BATCH; ++g) {
-            pl_u32x4 sv[PL_SLAB_BATCH];
+            sk_u32x4 sv[PL_SLAB_BATCH];
 #pragma unroll
             for (int e = 0; e < PL_SLAB_BATCH; ++e) sv[e] = __builtin_amdgcn_raw_buffer_load_b128(rs_src, base + (unsigned)((g * PL_SLAB_BATCH + e) * 1024), 0, 0);
 #pragma unroll
@@ -447,7 +409,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
       }
     }
     if (PL_DBG(16) && blockIdx.x == 8 && tid == 0) {         // tools: shader cycles and 100 MHz wall ticks of one workgroup's life so far
-      unsigned long long* o = reinterpret_cast<unsigned long long*>(p.ws + PL_MAX_WG + 2);
+      unsigned long long* o = reinterpret_cast<unsigned long long*>(p.ws + SK_MAX_WG + 2);
       o[0] = clock64() - dbg_c0;
       o[1] = wall_clock64() - dbg_w0;
     }
@@ -455,7 +417,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_kernel(const ctts_gemm_desc d,
     __builtin_amdgcn_s_waitcnt(0);
     if (!sk_next_piece(cu, rg.lo, nkb, cp)) break;
     ckb = cp.kb_lo;
-    zero_acc();
+    pl_zero_acc(acc);
     if constexpr (SKEW) { int r0_, c0_; decode(cp, r0_, c0_, idle); }
     read_frag(stage, 0, f0);            // the next piece's first block landed before the last barrier
   }
@@ -583,7 +545,7 @@ extern "C" bool ctts_gemm_pl_plan(const ctts_gemm_desc& d, PlArgs& p, GemmGrid& 
     W = 1;
   }
   const int grid = (int)W * 8;
-  if (grid > PL_MAX_WG || (long)grid * PL_SLAB > PL_SLAB_FLOATS_MAX) return false;
+  if (grid > SK_MAX_WG || (long)grid * PL_SLAB > SK_SLAB_FLOATS_MAX) return false;
   g.tile_m = PL_BM; g.tile_n = PL_BN;
   g.grid = grid;
   return true;

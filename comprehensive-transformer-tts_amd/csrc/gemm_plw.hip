@@ -21,7 +21,8 @@
 //   * ragged (b, t) rows: the K-blocks beyond an utterance's length are not part of the unit space at all (their dZ rows are zero by
 //     construction - the rule gemm_x6tn_kernel relies on); every workgroup builds the prefix sums of the active K-blocks from row_lens;
 //   * tile 128 x 256, 8 waves (2 x 4), six cross terms smallest first, two 72 KB stages, the mid-block barrier and the rotated
-//     instruction order of the upper wave group, the even unit partition and the fixed-order slab hand-off: as in gemm_pl.hip;
+//     instruction order of the upper wave group: as in gemm_pl.hip; the even unit partition (sk_plan.h) and the fixed-order slab
+//     hand-off (sk_handoff.h) are those of all stream-K kernels;
 //   * epilogue: C = alpha * acc or C += alpha * acc (what split_k > 1 without split_overwrite means in ctts_gemm) by the tile's owner -
 //     the weight gradient is added to param.grad in place, in a fixed order, without partial matrices and without a reduce launch.
 // Eligibility: ctts_gemm_plw_plan below; everything else stays on gemm_x6tn_kernel / the fp32 kernels.
@@ -45,8 +46,6 @@ static_assert(3 * (PLW_A_PLANE + PLW_B_PLANE) == PL_STAGE, "same stage size as g
 
 #define PLW_SGB12() __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0)
 #define PLW_INTERLEAVE_4x2() PLW_SGB12(); PLW_SGB12(); PLW_SGB12(); PLW_SGB12()
-
-struct PlwFrag { pl_u32x4 a[2][3], b[2][3]; };       // one 16-deep k-step: [MFMA row / column tile][piece]
 
 // TERMS: 6 = the six cross terms; 1 = the "amp" arithmetic of gemm_pl_kernel (hi pieces only)
 template <bool CONV, int TERMS>
@@ -92,13 +91,12 @@ __global__ __launch_bounds__(512, 2) void gemm_plw_kernel(const ctts_gemm_desc d
 
   const int T = CONV ? d.conv_T : 0x3FFFFFFF;
   const int cin = CONV ? d.conv_cin : 1;
-  const pl_i32x4 ra_src = pl_make_rsrc(d.A_planes);
-  const pl_i32x4 rb_src = pl_make_rsrc(d.B_planes - (CONV ? (long)d.conv_pad * d.ldb * 3 : 0));      // row 0 of the resource = row -pad
+  const sk_i32x4 ra_src = sk_make_rsrc(d.A_planes);
+  const sk_i32x4 rb_src = sk_make_rsrc(d.B_planes - (CONV ? (long)d.conv_pad * d.ldb * 3 : 0));      // row 0 of the resource = row -pad
   const unsigned lda2 = (unsigned)(d.lda * 6), ldb2 = (unsigned)(d.ldb * 6);
   const unsigned smem_addr = (unsigned)reinterpret_cast<uintptr_t>(smem);
   unsigned* flags = p.ws;
-  float* slabs = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(p.ws) + CTTS_WS_SLABS);
-  const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc((void*)slabs, 0, 0x7FFFFFFE, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_src = sk_slab_rsrc(p.ws);
 
   auto decode = [&](const SkPiece& pc, int& row0, int& col0) {
     int mslot, nt;
@@ -204,13 +202,13 @@ __global__ __launch_bounds__(512, 2) void gemm_plw_kernel(const ctts_gemm_desc d
     const unsigned sA = smem_addr + (unsigned)(stage * PL_STAGE + wave * 1024);
     const unsigned sB = smem_addr + (unsigned)(stage * PL_STAGE + 3 * PLW_A_PLANE + wave * 1024);       // instruction n = wave + 8 j
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) pl_dma16(ra_src, sA + q * PLW_A_PLANE, vA, l_soffA + q * 64);
+    for (int q = 0; q < NQ; ++q) sk_dma16(ra_src, sA + q * PLW_A_PLANE, vA, l_soffA + q * 64);
     if (!PL_DBG(64)) {                 // tools: 64 = no B DMA after the prologue (what would a smaller B image buy?)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
       if (wave + 8 * j < l_ni) {         // wave-uniform: a folded image is 3 - 5 instructions per piece, not 16
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) pl_dma16(rb_src, sB + q * PLW_B_PLANE + j * 8192, vB[j], l_soffB + q * 64);
+        for (int q = 0; q < NQ; ++q) sk_dma16(rb_src, sB + q * PLW_B_PLANE + j * 8192, vB[j], l_soffB + q * 64);
       }
     }
   };
@@ -258,7 +256,7 @@ __global__ __launch_bounds__(512, 2) void gemm_plw_kernel(const ctts_gemm_desc d
   };
 #pragma unroll
   for (int i = 0; i < 2; ++i) fa_off[i] = (8 * h + fsw) * (PL_BM * 2) + ((((wm0 >> 5) + i) ^ fsw) << 6) + fcol2;
-  auto read_frag = [&](int stage, int ks, PlwFrag& f) {
+  auto read_frag = [&](int stage, int ks, PlFrag& f) {
     const unsigned char* base = smem + stage * PL_STAGE;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -268,7 +266,7 @@ __global__ __launch_bounds__(512, 2) void gemm_plw_kernel(const ctts_gemm_desc d
         const plw_s16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((plw_lds_s16x4*)(pa));
         const plw_s16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((plw_lds_s16x4*)(pa + 4 * (PL_BM * 2)));
         const unsigned long long u0 = __builtin_bit_cast(unsigned long long, x0), u1 = __builtin_bit_cast(unsigned long long, x1);
-        f.a[i][q] = pl_u32x4{(unsigned)u0, (unsigned)(u0 >> 32), (unsigned)u1, (unsigned)(u1 >> 32)};
+        f.a[i][q] = sk_u32x4{(unsigned)u0, (unsigned)(u0 >> 32), (unsigned)u1, (unsigned)(u1 >> 32)};
       }
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -279,38 +277,10 @@ __global__ __launch_bounds__(512, 2) void gemm_plw_kernel(const ctts_gemm_desc d
         const plw_s16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((plw_lds_s16x4*)(pb));
         const plw_s16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((plw_lds_s16x4*)(pb + 4 * rs));
         const unsigned long long u0 = __builtin_bit_cast(unsigned long long, x0), u1 = __builtin_bit_cast(unsigned long long, x1);
-        f.b[j][q] = pl_u32x4{(unsigned)u0, (unsigned)(u0 >> 32), (unsigned)u1, (unsigned)(u1 >> 32)};
+        f.b[j][q] = sk_u32x4{(unsigned)u0, (unsigned)(u0 >> 32), (unsigned)u1, (unsigned)(u1 >> 32)};
       }
   };
   floatx16 acc[2][2];
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  };
-  auto mma_terms = [&](const PlwFrag& f, int t0, int t1) {
-    if constexpr (TERMS == 1) {          // hi x hi only
-      if (t0 <= 5 && 5 < t1) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = pl_mma(f.a[i][0], f.b[j][0], acc[i][j]);
-      }
-      return;
-    }
-#pragma unroll
-    for (int t = 0; t < 6; ++t) {
-      constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-      if (t < t0 || t >= t1) continue;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = pl_mma(f.a[i][PA[t]], f.b[j][PB[t]], acc[i][j]);
-    }
-  };
 
   // ---- prologue: blocks 0 and 1 in flight
   loader_set_piece();
@@ -325,12 +295,12 @@ __global__ __launch_bounds__(512, 2) void gemm_plw_kernel(const ctts_gemm_desc d
   sk_next_piece(cu, rg.lo, nkb, cp);
   int ckb = cp.kb_lo;
   { int r0_, c0_; decode(cp, r0_, c0_); set_b_frag(c0_ / PL_BN); }
-  zero_acc();
+  pl_zero_acc(acc);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   // the K loop in two instruction orders (lower / upper wave group), as in gemm_pl_kernel
   auto run = [&](auto skew_c) {
     constexpr bool SKEW = decltype(skew_c)::value;
-    PlwFrag f0, f1;
+    PlFrag f0, f1;
     read_frag(0, 0, f0);
     int stage = 0;
     __builtin_amdgcn_s_waitcnt(0);
@@ -339,10 +309,10 @@ __global__ __launch_bounds__(512, 2) void gemm_plw_kernel(const ctts_gemm_desc d
       // One fragment read per MFMA (sched_group_barrier): hipcc otherwise emits the 24 reads of a half block as two bursts, during which
       // the wave issues no MFMA - the matrix pipe then depends on the SIMD's other wave being in an MFMA phase at that moment (measured
       // without DMA: 314 us with the bursts, 253 us with no reads at all, dense FFN shape).
-      if (PL_DBG(256)) { if (do_mma) mma_terms(f0, 0, 6); }
+      if (PL_DBG(256)) { if (do_mma) pl_mma_terms<TERMS>(acc, f0, 0, 6); }
       else {
         read_frag(stage, 1, f1);
-        if (do_mma) mma_terms(f0, 0, 6);
+        if (do_mma) pl_mma_terms<TERMS>(acc, f0, 0, 6);
         if constexpr (TERMS == 1) { PLW_INTERLEAVE_4x2(); } else { PLW_INTERLEAVE_24(); }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -356,7 +326,7 @@ __global__ __launch_bounds__(512, 2) void gemm_plw_kernel(const ctts_gemm_desc d
       // (read unconditionally: when this block ends the piece the values are dead - f0 is read again behind the epilogue - and the reads
       //  and the MFMAs stay in ONE scheduling region)
       if (!PL_DBG(256)) read_frag(stage ^ 1, 0, f0);
-      if (do_mma) mma_terms(f1, 0, 6);
+      if (do_mma) pl_mma_terms<TERMS>(acc, f1, 0, 6);
       if constexpr (TERMS == 1) { PLW_INTERLEAVE_4x2(); } else { PLW_INTERLEAVE_24(); }
       __builtin_amdgcn_sched_barrier(0);
       if (have_l && !PL_DBG(1)) loader_issue(stage);
@@ -365,71 +335,15 @@ __global__ __launch_bounds__(512, 2) void gemm_plw_kernel(const ctts_gemm_desc d
       stage ^= 1;
       if (ckb < cp.kb_hi) continue;
 
-      // ---------------- the piece is complete (see gemm_pl_kernel for the laundering of the lane constants and of the descriptor)
-      int e_l31 = l31, e_h = h, e_wm0 = wm0, e_wn0 = wn0;
-      unsigned long long kargs = (unsigned long long)(const void*)__builtin_amdgcn_kernarg_segment_ptr();
-      asm volatile("" : "+v"(e_l31), "+v"(e_h), "+s"(e_wm0), "+s"(e_wn0), "+s"(kargs));
-      const ctts_gemm_desc& dc = *(const ctts_gemm_desc*)(const __attribute__((address_space(4))) ctts_gemm_desc*)kargs;
+      // ---------------- the piece is complete
+      PL_PIECE_COMPLETE();          // -> dc, e_l31, e_h, e_wm0, e_wn0: nothing below costs the K loop registers
       int row0, col0;
       decode(cp, row0, col0);
       if (cp.kb_hi < nkb) {
-        const unsigned base = (unsigned)blockIdx.x * (PL_SLAB * 4) + (unsigned)(wave * (PL_SLAB / 8) + lane * 4) * 4u;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              pl_u32x4 v;
-              v.x = __float_as_uint(acc[i][j][4 * q + 0]); v.y = __float_as_uint(acc[i][j][4 * q + 1]);
-              v.z = __float_as_uint(acc[i][j][4 * q + 2]); v.w = __float_as_uint(acc[i][j][4 * q + 3]);
-              __builtin_amdgcn_raw_buffer_store_b128(v, rs_src, base + (unsigned)(((i * 2 + j) * 4 + q) * 1024), 0, 16);      // aux 16 = sc1
-            }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store((pl_gu32*)(flags + blockIdx.x), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sk_slab_publish<2, 2, 8>(acc, rs_src, flags, wave, lane, tid);
       } else {
-        if (cp.kb_lo > 0) {
-          const int tile_lo = cp.t * nkb;
-          const int Ux = (rg.T1 - rg.T0) * nkb;
-          int upper = rg.lo;
-          for (int jj = wj - 1; jj >= 0 && upper > tile_lo; --jj) {
-            const int blo = sk_bound(g, Ux, jj);
-            if (blo >= upper) continue;
-            upper = blo;
-            const int src = jj * 8 + xcd;
-            if (tid == 0) {
-              unsigned spins = 0;
-              while (__hip_atomic_load((pl_gu32*)(flags + src), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 1u) {
-                __builtin_amdgcn_s_sleep(8);
-                if (++spins > (1u << 24)) {
-                  __hip_atomic_store((pl_gu32*)(flags + PL_MAX_WG), 1u + (unsigned)src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                  break;
-                }
-              }
-              __hip_atomic_store((pl_gu32*)(flags + src), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            const unsigned base = (unsigned)src * (PL_SLAB * 4) + (unsigned)(wave * (PL_SLAB / 8) + lane * 4) * 4u;
-            // all 16 loads of the slab in flight, THEN the sums (in the fixed order): written as "load, add" hipcc reused one register quad and
-            // waited for every load - 16 dependent L2 round trips, ~16 us per slab, on the critical path of every cut tile
-            pl_u32x4 sv[16];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sv[e] = __builtin_amdgcn_raw_buffer_load_b128(rs_src, base + (unsigned)(e * 1024), 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-              for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                  const pl_u32x4 v = sv[(i * 2 + j) * 4 + q];
-                  acc[i][j][4 * q + 0] += __uint_as_float(v.x); acc[i][j][4 * q + 1] += __uint_as_float(v.y);
-                  acc[i][j][4 * q + 2] += __uint_as_float(v.z); acc[i][j][4 * q + 3] += __uint_as_float(v.w);
-                }
-          }
-        }
+        // owner of a cut tile: all 16 loads of a slab in flight before their sums (this kernel affords the registers)
+        if (cp.kb_lo > 0) sk_slab_collect<2, 2, 8, 16>(acc, rs_src, flags, g, rg, cp, nkb, xcd, wj, wave, lane, tid);
         if (!PL_DBG(4)) {
           // C[m][n] = (C[m][n] +) alpha * acc: column l31 of a 32-wide MFMA tile, rows (r & 3) + 8 (r >> 2) + 4 h
 #pragma clang fp contract(off)
@@ -458,7 +372,7 @@ __global__ __launch_bounds__(512, 2) void gemm_plw_kernel(const ctts_gemm_desc d
       __builtin_amdgcn_s_waitcnt(0);
       if (!sk_next_piece(cu, rg.lo, nkb, cp)) break;
       ckb = cp.kb_lo;
-      zero_acc();
+      pl_zero_acc(acc);
       { int r0_, c0_; decode(cp, r0_, c0_); set_b_frag(c0_ / PL_BN); }
       read_frag(stage, 0, f0);            // the next piece's first block landed before the last barrier
     }
@@ -526,7 +440,7 @@ extern "C" bool ctts_gemm_plw_plan(const ctts_gemm_desc& d, PlwArgs& p, GemmGrid
   if (W > Wu) W = Wu;
   if (W < 1) W = 1;
   const int grid = (int)W * 8;
-  if (grid > PL_MAX_WG || (long)grid * PL_SLAB > PL_SLAB_FLOATS_MAX) return false;
+  if (grid > SK_MAX_WG || (long)grid * PL_SLAB > SK_SLAB_FLOATS_MAX) return false;
   g.tile_m = PL_BM; g.tile_n = PL_BN;
   g.grid = grid;
   return true;

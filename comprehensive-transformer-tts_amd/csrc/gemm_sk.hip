@@ -17,44 +17,14 @@
 // operands, conv views with cin % 32 == 0.  Everything else stays on gemm.hip.
 #include "ctts_common.h"
 #include "gemm_common.h"
-#include "sk_plan.h"
+#include "sk_handoff.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-typedef unsigned int sk_u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned int sk_gu32;
-typedef __attribute__((address_space(3))) void sk_lds_void;
-
 constexpr unsigned SK_OOB = 0x80000000u;
-constexpr int SK_FLAG_WORDS = 4096;            // header of the workspace: flags[0..2047], error word at [2048]
-constexpr int SK_SLAB_FLOATS_MAX = 2048 * 4096; // slab area: grid x (BM x BN) floats never exceeds this (host check)
-constexpr int SK_MAX_WG = 2048;
-
-typedef int sk_i32x4 __attribute__((ext_vector_type(4)));
-
-// raw buffer descriptor (2 GiB window, 32-bit raw-buffer format) as four SGPR words for the inline-asm DMA below
-__device__ __forceinline__ sk_i32x4 sk_make_rsrc(const void* base) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-  sk_i32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
-  r.z = 0x7FFFFFFE;
-  r.w = 0x00020000;
-  return r;
-}
-
-// One LDS-DMA instruction: 64 lanes x 16 bytes, global (descriptor + voff + soff) -> LDS [lds_addr + lane * 16).  Inline asm on purpose:
-// hipcc's waitcnt pass knows nothing about it, so it does not put `s_waitcnt vmcnt(0)` in front of every ds_read that follows (it does
-// for the builtin, because it cannot prove that the DMA target and the fragment reads are different LDS stages), and the loop's own
-// `s_waitcnt vmcnt(N)` + `s_barrier` stay the only synchronisation between the DMA and its readers.
-__device__ __forceinline__ void sk_dma16(sk_i32x4 rsrc, unsigned lds_addr, unsigned voff, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(soff))
-               : "memory");      // m0 is not on the clobber list (hipcc rejects reserved registers there); nothing else in this
-                                 // translation unit uses m0 - check the ISA (grep m0) when adding LDS-direct / GWS / movrel code
-}
+constexpr int SK_FLAG_WORDS = 4096;            // header of the workspace: flags[0..2047], error word at [2048] (sk_handoff.h)
 
 // r mod T for 0 <= r < 2^24 without the integer-division sequence
 __device__ __forceinline__ int sk_mod(int r, int T, float rcpT) {
@@ -168,7 +138,6 @@ __global__ __launch_bounds__(256, (MT * NT >= 4 ? 2 : ((MT * NT >= 2 || STAGES >
   constexpr int BM = 64 * MT, BN = 64 * NT, WM = 32 * MT, WN = 32 * NT;
   constexpr int A_FLOATS = BM * 32, STAGE_FLOATS = (BM + BN) * 32;
   constexpr int N_DMA = 2 * (MT + NT);                      // DMA instructions per K-block and wave
-  constexpr int SLAB = BM * BN;
   __shared__ __attribute__((aligned(16))) float smem[STAGES * STAGE_FLOATS];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -210,8 +179,7 @@ __global__ __launch_bounds__(256, (MT * NT >= 4 ? 2 : ((MT * NT >= 2 || STAGES >
   const sk_i32x4 rb_src = sk_make_rsrc(d.B - (CONV_B ? (long)d.conv_pad * d.ldb : 0));
   const unsigned smem_addr = (unsigned)reinterpret_cast<uintptr_t>(smem);      // low word of the flat address = LDS byte address
   unsigned* flags = p.ws;
-  float* slabs = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(p.ws) + CTTS_WS_SLABS);      // shared slab area of the workspace (ctts_common.h)
-  const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc((void*)slabs, 0, 0x7FFFFFFE, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_src = sk_slab_rsrc(p.ws);
   const int T = d.conv_T > 0 ? d.conv_T : 1;
   const float rcpT = 1.0f / (float)T;
   const int cin = d.conv_cin > 0 ? d.conv_cin : 32;
@@ -348,65 +316,10 @@ __global__ __launch_bounds__(256, (MT * NT >= 4 ? 2 : ((MT * NT >= 2 || STAGES >
     int row0, col0;
     decode(cp, row0, col0);
     if (cp.kb_hi < nkb) {
-      // contribution: slab (write-through stores) + flag
-      const unsigned base = (unsigned)blockIdx.x * (SLAB * 4) + (unsigned)(wave * (SLAB / 4) + lane * 4) * 4u;
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            sk_u32x4 v;
-            v.x = __float_as_uint(acc[i][j][4 * q + 0]); v.y = __float_as_uint(acc[i][j][4 * q + 1]);
-            v.z = __float_as_uint(acc[i][j][4 * q + 2]); v.w = __float_as_uint(acc[i][j][4 * q + 3]);
-            __builtin_amdgcn_raw_buffer_store_b128(v, rs_src, base + (unsigned)(((i * NT + j) * 4 + q) * 1024), 0, 16);      // aux 16 = sc1
-          }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) __hip_atomic_store((sk_gu32*)(flags + blockIdx.x), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      sk_slab_publish<MT, NT, 4>(acc, rs_src, flags, wave, lane, tid);
     } else {
-      if (cp.kb_lo > 0) {
-        // owner of a cut tile: add the slabs of the workgroups below, nearest first, until the tile's unit 0 is covered
-        const int tile_lo = cp.t * nkb;
-        const int Ux = (rg.T1 - rg.T0) * nkb;
-        int upper = rg.lo;                                   // start of the range that is already summed
-        for (int jj = wj - 1; jj >= 0 && upper > tile_lo; --jj) {
-          const int blo = sk_bound(g, Ux, jj);
-          if (blo >= upper) continue;                        // empty range: that workgroup published nothing
-          upper = blo;
-          const int src = jj * 8 + xcd;
-          if (tid == 0) {
-            unsigned spins = 0;
-            while (__hip_atomic_load((sk_gu32*)(flags + src), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 1u) {
-              __builtin_amdgcn_s_sleep(8);
-              if (++spins > (1u << 24)) {                    // bounded: report instead of hanging
-                __hip_atomic_store((sk_gu32*)(flags + SK_MAX_WG), 1u + (unsigned)src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-              }
-            }
-            __hip_atomic_store((sk_gu32*)(flags + src), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // self-cleaning
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          }
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          __syncthreads();
-          const unsigned base = (unsigned)src * (SLAB * 4) + (unsigned)(wave * (SLAB / 4) + lane * 4) * 4u;
-          // the four loads of an MFMA tile in flight, then their sums (fixed order): as "load, add" hipcc reused one register quad and
-          // waited for every load - MT * NT * 4 dependent L2 round trips (~1 us each) per slab on the critical path of every cut tile
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-              sk_u32x4 sv[4];
-#pragma unroll
-              for (int q = 0; q < 4; ++q) sv[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_src, base + (unsigned)(((i * NT + j) * 4 + q) * 1024), 0, 0);
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                acc[i][j][4 * q + 0] += __uint_as_float(sv[q].x); acc[i][j][4 * q + 1] += __uint_as_float(sv[q].y);
-                acc[i][j][4 * q + 2] += __uint_as_float(sv[q].z); acc[i][j][4 * q + 3] += __uint_as_float(sv[q].w);
-              }
-            }
-        }
-      }
+      // owner of a cut tile; the four loads of an MFMA tile in flight before their sums
+      if (cp.kb_lo > 0) sk_slab_collect<MT, NT, 4, 4>(acc, rs_src, flags, g, rg, cp, nkb, xcd, wj, wave, lane, tid);
       if (p.accumulate) {
         gemm_accumulate_lean<MT, NT>(d, acc, d.C, row0, col0, wm0, wn0, l31, h, d.M, d.N);
       } else if (!(p.debug & 4)) {
@@ -480,7 +393,6 @@ extern "C" const uint32_t* ctts_workspace_error_word(const void* ws) {
   return ws ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const unsigned char*>(ws) + CTTS_WS_SK_FLAGS) + SK_MAX_WG : nullptr;
 }
 static_assert((size_t)SK_FLAG_WORDS * 4 <= CTTS_WS_GEMM_TICKETS, "stream-K flag words overlap the split-K tickets");
-static_assert((size_t)SK_SLAB_FLOATS_MAX <= CTTS_WS_SLAB_FLOATS, "stream-K slabs exceed the workspace slab area");
 
 // eligibility, tile and grid of the persistent kernel
 extern "C" bool ctts_gemm_sk_plan(const ctts_gemm_desc& d, SkArgs& p, GemmGrid& g) {

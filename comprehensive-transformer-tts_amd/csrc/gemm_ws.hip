@@ -7,7 +7,7 @@
 //   * a workgroup of 4 waves owns 128 output columns; wave w keeps the B fragments of ITS 32 columns for all of K in 16 * K/32 = 128
 //     VGPRs, loaded once per launch straight from global memory in MFMA fragment order;
 //   * the workgroup is persistent over 64-row tiles of A.  A tile arrives as two K-halves (64 rows x 128 floats = 32 KB each) in two
-//     LDS stages by DMA (buffer_load ... lds, issued from inline asm as in gemm_sk.hip): while the waves run the 128 MFMAs of one half,
+//     LDS stages by DMA (buffer_load ... lds, issued from inline asm as in sk_handoff.h): while the waves run the 128 MFMAs of one half,
 //     the other half (of this tile or of the next one) is in flight - one barrier per 128 MFMAs of every wave;
 //   * every wave alternates between two accumulators (rows 0-31 / 32-63 of the tile) - the regime in which the matrix pipe keeps its
 //     full rate (tools/ubench/mfma_patterns.hip), fragment reads one group of 8 MFMAs ahead; 2 workgroups per CU (64 KB LDS,
@@ -22,27 +22,17 @@
 // zero-filled.  Eligibility: ctts_gemm_ws_plan.
 #include "ctts_common.h"
 #include "gemm_common.h"
+#include "sk_handoff.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-typedef int ws_i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int ws_u32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned WS_OOB = GEMM_OOB;
 
-__device__ __forceinline__ ws_i32x4 ws_make_rsrc(const void* base) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-  ws_i32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
-  r.z = 0x7FFFFFFE;
-  r.w = 0x00020000;
-  return r;
-}
-
-// see gemm_sk.hip sk_dma16: inline asm keeps hipcc from draining the DMA in front of the fragment reads
-__device__ __forceinline__ void ws_dma16(ws_i32x4 rsrc, unsigned lds_addr, unsigned voff) {
+// see sk_dma16 (sk_handoff.h; the buffer descriptor is its sk_make_rsrc): inline asm keeps hipcc from draining the DMA in front of the
+// fragment reads.  This form has no scalar offset operand.
+__device__ __forceinline__ void ws_dma16(sk_i32x4 rsrc, unsigned lds_addr, unsigned voff) {
   asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
                :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc) : "memory");
 }
@@ -94,7 +84,7 @@ __global__ __launch_bounds__(256, 2) void gemm_ws_kernel(const ctts_gemm_desc d,
       }
     }
   }
-  const ws_i32x4 ra_src = ws_make_rsrc(d.A);
+  const sk_i32x4 ra_src = sk_make_rsrc(d.A);
   const unsigned smem_addr = (unsigned)reinterpret_cast<uintptr_t>(smem);
   // DMA mapping: wave w moves K-blocks w, w + 4, ... of the half; per K-block 8 instructions of 8 rows x 128 bytes
   const int r_in = lane >> 3;                           // row inside an 8-row group

@@ -194,6 +194,27 @@ def test_plane_gemm_data_gradient_shape_long_reduction_with_halo_vs_fp64(ragged)
     assert torch.equal(got, again) and _err_word() == 0
 
 
+def test_plane_gemm_slab_hand_off_is_exact_on_integers():
+    """Every tile cut into four pieces, the owner adding three slabs: integers in [-2048, 2048] (hi and mid pieces non-zero) against
+    {-1, 0, 1} over K = 4096 - every partial sum, of a piece or of pieces added up, is an exact integer of magnitude <= 2^23, so the
+    result equals the float64 product bit for bit and a mis-mapped quad or a dropped slab shows as the actual difference.
+    Partition (ctts_gemm_pl_plan, no environment override): M = 128, N = 1024 -> 1 x 4 tiles of 128 x 256, nkb = 4096 / 32 = 128 K-blocks,
+    512 units; bf16_split = 2 lifts the size thresholds; nkb >= 24, so tiles may be cut, into at most 8 pieces; W = min(32,
+    units / (8 * 16) = 4, tiles * 8 / 8 = 4) = 4 workgroups per XCD, grid 32.  XCD x owns the tiles [x * 4 / 8, (x + 1) * 4 / 8): XCDs 1, 3,
+    5, 7 one tile each (128 units), the others none; workgroup j of such an XCD owns K-blocks [32 j, 32 j + 32): workgroups 0 .. 2 publish
+    a slab each, workgroup 3 owns the tile and collects the slabs of 2, 1, 0 in that order."""
+    M, N, Kd = 128, 1024, 4096
+    g = torch.Generator().manual_seed(41)
+    A = torch.randint(-2048, 2049, (M, Kd), generator=g).float()
+    Bm = torch.randint(-1, 2, (N, Kd), generator=g).float()
+    ref = A.double() @ Bm.double().t()
+    got = _plane_gemm(A.to(DEV), Bm.to(DEV), M, N, Kd, bf16_split=2)                  # C pre-filled with NaN
+    bad = (got.double().cpu() != ref).nonzero()
+    assert torch.equal(got.double().cpu(), ref), f"{len(bad)} elements differ, first (row, column) {bad[0].tolist()}: " \
+        f"{float(got[tuple(bad[0])])} vs {float(ref[tuple(bad[0])])}"
+    assert _err_word() == 0
+
+
 def test_plane_gemm_is_refused_where_it_does_not_apply_and_the_launch_still_runs():
     """Descriptors the plane kernel does not carry (bf16_split = 0, an epilogue outside its set, N not a multiple of 128) run on the other
     kernels from the fp32 operands - same result."""

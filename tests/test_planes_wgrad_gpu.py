@@ -133,6 +133,33 @@ def test_cut_tiles_hand_their_partial_sums_over_in_a_fixed_order():
     K.WorkspaceErrorProbe().poll_and_check()
 
 
+@pytest.mark.parametrize("accumulate", [False, True])
+def test_slab_hand_off_is_exact_on_integers(accumulate):
+    """Every tile cut into four pieces, the owner adding three slabs: dZ holds integers in [-2048, 2048] (hi and mid pieces non-zero), X
+    entries in {-1, 0, 1}, 4096 rows - every partial sum, of a piece or of pieces added up, is an exact integer of magnitude <= 2^23, so
+    the result equals the float64 product bit for bit and a mis-mapped quad or a dropped slab shows as the actual difference.  Overwrite
+    (C pre-filled with NaN) and accumulate (C pre-filled with an integer: the constant plus the product, still below 2^24).
+    Partition (ctts_gemm_plw_plan, no environment override): cout = 256, cin = 512 -> 2 x 2 tiles of 128 x 256, nkb = 4096 / 32 = 128
+    K-blocks, 512 units; bf16_split = 2 lifts the size and tile-count thresholds; W = min(32, units / (8 * 16) = 4) = 4 workgroups per
+    XCD, grid 32.  XCD x owns the tiles [x * 4 / 8, (x + 1) * 4 / 8): XCDs 1, 3, 5, 7 one tile each (128 units), the others none;
+    workgroup j of such an XCD owns K-blocks [32 j, 32 j + 32): workgroups 0 .. 2 publish a slab each, workgroup 3 owns the tile and
+    collects the slabs of 2, 1, 0 in that order."""
+    rows, cout, cin = 4096, 256, 512
+    g = torch.Generator().manual_seed(42)
+    dZ = torch.randint(-2048, 2049, (rows, cout), generator=g).float()
+    X = torch.randint(-1, 2, (rows, cin), generator=g).float()
+    ref = ref_wgrad(dZ, X, 0, 0, 0)
+    if accumulate:
+        ref = ref + 7.0
+        got = plane_wgrad(dZ.to(DEV), X.to(DEV), cout, cin, out=torch.full((cout, cin), 7.0, device=DEV), bf16_split=2, split_k=2)
+    else:
+        got = plane_wgrad(dZ.to(DEV), X.to(DEV), cout, cin, bf16_split=2, split_k=2, split_overwrite=True)      # C pre-filled with NaN
+    bad = (got.double().cpu() != ref).nonzero()
+    assert torch.equal(got.double().cpu(), ref), f"{len(bad)} elements differ, first (row, column) {bad[0].tolist()}: " \
+        f"{float(got[tuple(bad[0])])} vs {float(ref[tuple(bad[0])])}"
+    assert max(int(ws.view(torch.int32)[2048].item()) for ws in K._SK_WS.values()) == 0          # the hand-off error word
+
+
 def test_full_size_ffn_weight_gradient_against_the_other_kernels():
     """the launch of the fs2 step (decoder FFN conv k = 9, 256 -> 1024, 16 x 1024 ragged rows): plane kernel vs the in-kernel-split kernel
     vs fp32 MFMA on the same operands"""
