@@ -38,6 +38,13 @@ int ctts_version(void);
  *   - STFT-as-conv1d + mel matmul  audio/stft.py:72-80,177
  * Conv view: rows of the operand are (b,t) pairs with t = row % conv_T; element (row, kk)
  * reads X[(row - conv_pad)*ld + kk] and is zero unless 0 <= t - conv_pad + kk/conv_cin < conv_T.
+ * The viewed operand is dense, ld == conv_cin (a K index runs on into the next rows; with another ld the kernel families address
+ * different elements), and made of whole utterances: its row count (M, or K with conv_on_b) is a multiple of conv_T, because the
+ * zero test looks at t alone.
+ * Rules every kernel family follows (tests/gemm_restate64.py restates the descriptor in float64, tests/test_gemm_contract_gpu.py holds
+ * every route kind to it): bias, R, Z and rowscale are NOT batched - every batch reads R[m*ldr + n] and rowscale[m] and stores
+ * Z[m*ldz + n]; the dropout element index is batch*M*N + m*N + n with the descriptor's M and N, in 32 bits (wrapping); cells of C and
+ * Z outside the [M, N] block of a batch (columns N .. ld-1, other rows, the gaps between batches) are never written.
  */
 typedef struct ctts_gemm_desc {
   const float* A; const float* B; float* C;
@@ -49,7 +56,8 @@ typedef struct ctts_gemm_desc {
   const int32_t* lens;                    /* [nb0] valid length per z0, or NULL                       */
   int32_t lim_m, lim_n, lim_k;            /* clamp that dim to lens[z0]                               */
   int32_t conv_T, conv_pad, conv_cin, conv_on_b; /* conv_T=0: plain; conv_on_b=1 applies to B (b_kc=0) */
-  int32_t split_k;                        /* >1: C += alpha * A B, K cut into <= split_k pieces summed in a FIXED order through sk_ws (no atomics, no epilogue) */
+  int32_t split_k;                        /* >1: C += alpha * A B, K cut into <= split_k pieces summed in a FIXED order through sk_ws (no atomics, no epilogue:
+                                             pass no bias / act / Z / dropout / R / rowscale with it - the tile kernels ignore them, the persistent ones may not) */
   float alpha;
   const float* bias;                      /* [N] or NULL                                              */
   float* Z; int64_t ldz;                  /* optional store of the pre-activation                     */
@@ -60,7 +68,13 @@ typedef struct ctts_gemm_desc {
   /* Padded-row skipping.  Rows (of C for a_kc=1, of the reduction dim for the TN layout) are (b,t) pairs,
    * t = row % row_T; rows with t >= row_lens[b] + row_halo are padding whose result is defined as ZERO:
    * whole output tiles of such rows are zero-filled without touching the operands (a_kc=1), and K-blocks
-   * of such rows are skipped in weight-gradient reductions (a_kc=0, b_kc=0).  NULL = off.               */
+   * of such rows are skipped in weight-gradient reductions (a_kc=0, b_kc=0).  NULL = off.
+   * Only WHOLE tiles (tile_m rows of the kernel that runs, ctts_gemm_route) and whole K-blocks are skipped; a padded row that shares a
+   * tile with a live row is computed from the operands like any other.  It is the CALLER's duty to pass operands whose result is zero
+   * there: the rows of A beyond length + halo are zero (and no bias, or a zero rowscale, reaches them) - then every padded row of C
+   * (and of a stored Z) is zero whichever kernel runs.  For the TN layout the rows of A (dZ) in the padding MUST be exactly zero:
+   * the two-group kernel (kind BUF_K2) skips nothing and multiplies them.  With split_k > 1 a skipped tile adds nothing to C, or
+   * stores zero under split_overwrite. */
   const int32_t* row_lens; int32_t row_T; int32_t row_halo;
   /* Optional m-tile schedule for row_lens launches (ctts_row_tile_map, 64-row tiles): tile_map[0] = number of ACTIVE m-tiles,
    * tile_map[1..] = m-tile indices, active ones first.  Workgroup b then works on m-tile tile_map[1 + b / tiles_n] and n-tile
@@ -74,7 +88,9 @@ typedef struct ctts_gemm_desc {
   int32_t tile_group_n;
   /* Optional softmax-backward fusion (attention): C = E * (alpha * acc - rowsub[row]) with E laid out exactly like C (same ldc and
    * batch strides) and rowsub indexed [batch * M + row]:  dS = P * (dP - D), D = rowsum(dO * O), straight out of the dP = dO V^T GEMM -
-   * no separate pass over the [T,T] maps.  NULL = off; not combinable with bias / act / dropout / R / rowscale / split_k. */
+   * no separate pass over the [T,T] maps.  NULL = off; not combinable with bias / act / dropout / R / rowscale / split_k.  E is addressed
+   * from its own pointer (batch strides, m*ldc + n): an element offset folded into the C pointer is not applied to it; rowsub uses the
+   * descriptor's M also where lens cut a batch shorter. */
   const float* E; const float* rowsub;
   /* Workspace (ctts_workspace_bytes() bytes, zero-filled ONCE by the caller, private to the stream the launch goes to: launches that
    * share it must be stream-ordered; every kernel leaves its flag / ticket words at zero).  REQUIRED when split_k > 1: the partial tiles
