@@ -3,6 +3,10 @@
 Tensors are only used for device memory + the current stream; every call goes through
 libctts_hip.so.  Inputs must live on a HIP device ("cuda" in PyTorch-ROCm) - a CPU tensor
 raises: there is no CPU path in the product.
+
+`gemm` is ctts_gemm_desc spelled out (sizes, leading dimensions, layout flags, element offsets, batch counts and strides); `bgemm` is the
+same launch described by three tensor views, from which `gemm_views` derives those fields - callers that hold plain strided matrices
+(attention products, bmm, slices of a packed tensor) say what they compute and cannot mis-spell a stride.
 """
 import collections
 import ctypes as C
@@ -316,7 +320,57 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, defer=False, 
     return Cout
 
 
-GemmRoute = collections.namedtuple("GemmRoute", "kind tile_m tile_n split_k k_granule")
+def _matrix_view(t, name, nb):
+    """(row_major, ld, batch strides) of the float32 view `t` [..., R, Cc] under the batch sizes `nb` of the output (broadcast like torch:
+    levels are matched from the right; an absent, size-1 or expanded level has stride 0).  A matrix is row-major when its columns are
+    contiguous (or there is one), column-major when its rows are; the stride of a size-1 dimension means nothing, the dense value stands
+    in for it."""
+    if t.dtype != torch.float32 or t.dim() < 2 or t.dim() - 2 > len(nb):
+        raise _lib.CttsError(f"{name}: expected a float32 matrix view with at most {len(nb)} batch dimensions, got {t.dtype} {tuple(t.shape)}")
+    (R, Cc), (sr, sc), lead = t.shape[-2:], t.stride()[-2:], t.shape[:-2]
+    if sc == 1 or Cc == 1:
+        row_major, ld = True, (sr if R > 1 else Cc)
+    elif sr == 1 or R == 1:
+        row_major, ld = False, sc
+    else:
+        raise _lib.CttsError(f"{name}: neither rows nor columns are contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
+    if any(n not in (1, want) for n, want in zip(lead, nb[len(nb) - len(lead):])):
+        raise _lib.CttsError(f"{name}: batch sizes {tuple(lead)} neither equal nor broadcast to the output's {tuple(nb)}")
+    strides = [0] * (len(nb) - len(lead)) + [s if n > 1 else 0 for n, s in zip(lead, t.stride())]
+    return row_major, ld, tuple(strides + [0] * (2 - len(nb)))
+
+
+def gemm_views(A, B, Cout, E=None, lens=None):
+    """The launch `Cout = A @ B` described by views: A = op(A) [..., M, K], B = op(B) [..., K, N], Cout [..., M, N] with 0, 1 or 2 leading
+    batch dimensions -> (args, kw), the positional arguments and the nb0 / nb1 / sA / sB / sC keywords of gemm (and of gemm_route and the
+    gemm_takes_* queries).  Leading dimensions, transposition flags and batch strides are read off the views; a view's data_ptr()
+    includes its storage offset, so no *_off is needed.  Host-only, any device; refuses what ctts_gemm_desc cannot express.  E / lens:
+    checked only (the epilogue operand must be laid out exactly like Cout, lens holds one length per nb0)."""
+    nb = tuple(Cout.shape[:-2])
+    if len(nb) > 2:
+        raise _lib.CttsError(f"C: at most two batch dimensions, got shape {tuple(Cout.shape)}")
+    (a_rm, lda, sA), (b_rm, ldb, sB), (c_rm, ldc, sC) = (_matrix_view(t, n, nb) for t, n in ((A, "A"), (B, "B"), (Cout, "C")))
+    (M, Kd), N = A.shape[-2:], B.shape[-1]
+    if B.shape[-2] != Kd or tuple(Cout.shape[-2:]) != (M, N):
+        raise _lib.CttsError(f"inner extents disagree: A {tuple(A.shape)} @ B {tuple(B.shape)} -> C {tuple(Cout.shape)}")
+    if not c_rm or (N > 1 and Cout.stride(-1) != 1):
+        raise _lib.CttsError(f"C: the output needs unit column stride, got strides {Cout.stride()}")
+    if E is not None and (E.shape != Cout.shape or _matrix_view(E, "E", nb) != (c_rm, ldc, sC)):
+        raise _lib.CttsError(f"E: must be laid out exactly like C {tuple(Cout.shape)} {Cout.stride()}, got {tuple(E.shape)} {E.stride()}")
+    nb0, nb1 = nb + (1,) * (2 - len(nb))
+    if lens is not None and lens.numel() != nb0:
+        raise _lib.CttsError(f"lens: {lens.numel()} lengths for nb0 = {nb0} batches")
+    return (A, B, Cout, M, N, Kd, lda, ldb, ldc, a_rm, not b_rm), dict(nb0=nb0, nb1=nb1, sA=sA, sB=sB, sC=sC)
+
+
+def bgemm(A, B, Cout, **kw):
+    """gemm with the operands given as tensor views (gemm_views): `bgemm(P.transpose(-1, -2), dO, dV)` is dV = P^T dO.  Every other
+    keyword of gemm passes through untouched."""
+    args, views = gemm_views(A, B, Cout, kw.get("E"), kw.get("lens"))
+    return gemm(*args, **views, **kw)
+
+
+GemmRoute =collections.namedtuple("GemmRoute", "kind tile_m tile_n split_k k_granule")
 
 
 def gemm_route(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, **kw):

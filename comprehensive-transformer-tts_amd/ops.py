@@ -674,7 +674,7 @@ class _PackedLinear(torch.autograd.Function):
         wd = [w.detach() for w in ws]
         W = torch.as_strided(wd[0], (N, Kd), (Kd, 1)) if _adjacent(wd) else torch.cat(wd, 0)
         out = torch.empty(*x.shape[:-1], N, dtype=torch.float32, device=x.device)
-        K.gemm(x, W, out, M, N, Kd, Kd, Kd, N, True, True)
+        K.bgemm(x.view(M, Kd), W.t(), out.view(M, N))
         ctx.save_for_backward(x, *ws)
         ctx.sizes = sizes
         return out
@@ -682,20 +682,20 @@ class _PackedLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dY):
         x, ws = ctx.saved_tensors[0], ctx.saved_tensors[1:]
-        dY = dY.contiguous()
         Kd = x.shape[-1]
         M = x.numel() // Kd
         N = sum(ctx.sizes)
+        dY = dY.contiguous().view(M, N)
         wd = [w.detach() for w in ws]
         W = torch.as_strided(wd[0], (N, Kd), (Kd, 1)) if _adjacent(wd) else torch.cat(wd, 0)
         dX = None
         if ctx.needs_input_grad[0]:
             dX = torch.empty_like(x)
-            K.gemm(dY, W, dX, M, Kd, N, N, Kd, Kd, True, False)
+            K.bgemm(dY, W, dX.view(M, Kd))
         gs = [_grad_of(w) for w in ws]
         if all(g is not None for g in gs) and _adjacent(gs):
             G = torch.as_strided(gs[0], (N, Kd), (Kd, 1))
-            K.gemm(dY, x, G, N, Kd, M, N, Kd, Kd, False, False, split_k=max(2, _split_k_for(N, Kd, M)), defer=_WGRAD["stream"] is None)
+            K.bgemm(dY.t(), x.view(M, Kd), G, split_k=max(2, _split_k_for(N, Kd, M)), defer=_WGRAD["stream"] is None)
             return (dX,) + (None,) * len(ws)
         return (dX,) + tuple(_matmul_wgrad(dY, x, W).split(ctx.sizes, 0))      # W is detached: always a fresh tensor
 
@@ -826,6 +826,12 @@ class _FusedSelfAttention(torch.autograd.Function):
         return K.mha_bwd(qkv, lens, out, dO.contiguous(), lse, H, dh ** -0.5, qs), None, None
 
 
+def _heads(x, H, parts=1):
+    """the [B, H, T, dh] views of the `parts` channel blocks of x [B, T, parts * H * dh] (qkv: q, k, v; kv: k, v)"""
+    B, T, Cc = x.shape
+    return x.view(B, T, parts, H, Cc // (parts * H)).permute(2, 0, 3, 1, 4).unbind(0)
+
+
 class _SelfAttention(torch.autograd.Function):
     """Multi-head self-attention core on the packed projection qkv [B,T,3C] with a key-padding
     mask given as valid lengths (F.multi_head_attention_forward semantics,
@@ -839,16 +845,16 @@ class _SelfAttention(torch.autograd.Function):
         B, T, C3 = qkv.shape
         C = C3 // 3
         dh = C // n_heads
-        scale = dh ** -0.5
+        q, k, v = _heads(qkv, n_heads, 3)
         S = torch.empty(B, n_heads, T, T, dtype=torch.float32, device=qkv.device)
-        K.gemm(qkv, qkv, S, T, T, dh, C3, C3, T, True, True, a_off=0, b_off=C, nb0=B, nb1=n_heads,
-               sA=(T * C3, dh), sB=(T * C3, dh), sC=(n_heads * T * T, T * T), lens=lens, lim=(1, 1, 0), alpha=scale)
+        # S[q,key] = scale * sum_d Q[q,d] K[key,d]
+        K.bgemm(q, k.transpose(-1, -2), S, lens=lens, lim=(1, 1, 0), alpha=dh ** -0.5)
         K.softmax_fwd(S, lens, B, n_heads, T)
         sk = _attn_split_k(B * n_heads, T, dh)
         # "write everything" (split_overwrite): the query rows >= len are written as zeros by the launch itself - no fill launch
         out = torch.empty(B, T, C, dtype=torch.float32, device=qkv.device)
-        K.gemm(S, qkv, out, T, dh, T, T, C3, C, True, False, b_off=2 * C, nb0=B, nb1=n_heads,
-               sA=(n_heads * T * T, T * T), sB=(T * C3, dh), sC=(T * C, dh), lens=lens, lim=(1, 0, 1), split_k=sk, split_overwrite=True)
+        # O[q,d] = sum_key P[q,key] V[key,d]
+        K.bgemm(S, v, _heads(out, n_heads)[0], lens=lens, lim=(1, 0, 1), split_k=sk, split_overwrite=True)
         ctx.save_for_backward(qkv, S, lens, out)
         ctx.n_heads = n_heads
         return out
@@ -859,27 +865,22 @@ class _SelfAttention(torch.autograd.Function):
         H = ctx.n_heads
         dO = dO.contiguous()
         B, T, C3 = qkv.shape
-        C = C3 // 3
-        dh = C // H
+        dh = C3 // 3 // H
         scale = dh ** -0.5
-        sP = (H * T * T, T * T)
         sk = _attn_split_k(B * H, T, dh)
         dqkv = torch.empty_like(qkv)            # the three launches below write all of it ("write everything": zeros beyond each utterance's length)
+        (q, k, v), (dq, dk, dv), (dOh,) = _heads(qkv, H, 3), _heads(dqkv, H, 3), _heads(dO, H)
         # dV[key,d] = sum_q P[q,key] dO[q,d]
-        K.gemm(P, dO, dqkv, T, dh, T, T, C, C3, False, False, c_off=2 * C, nb0=B, nb1=H, sA=sP, sB=(T * C, dh),
-               sC=(T * C3, dh), lens=lens, lim=(1, 0, 1), split_k=sk, split_overwrite=True)
+        K.bgemm(P.transpose(-1, -2), dOh, dv, lens=lens, lim=(1, 0, 1), split_k=sk, split_overwrite=True)
         # dS[q,key] = P * (dO V^T - D),  D[q] = sum_key dP P = sum_d dO[q,d] O[q,d]: the softmax backward rides in the epilogue of the
         # dP GEMM (one read of P) instead of a separate pass that re-reads P and dP and rewrites dS
         Dv = K.rowdot_heads(dO, O, H)
         dP = torch.empty_like(P)
-        K.gemm(dO, qkv, dP, T, T, dh, C, C3, T, True, True, b_off=2 * C, nb0=B, nb1=H, sA=(T * C, dh), sB=(T * C3, dh),
-               sC=sP, lens=lens, lim=(1, 1, 0), E=P, rowsub=Dv)
+        K.bgemm(dOh, v.transpose(-1, -2), dP, lens=lens, lim=(1, 1, 0), E=P, rowsub=Dv)
         # dQ[q,d] = scale * sum_key dS[q,key] K[key,d]
-        K.gemm(dP, qkv, dqkv, T, dh, T, T, C3, C3, True, False, b_off=C, c_off=0, nb0=B, nb1=H, sA=sP, sB=(T * C3, dh),
-               sC=(T * C3, dh), lens=lens, lim=(1, 0, 1), alpha=scale, split_k=sk, split_overwrite=True)
+        K.bgemm(dP, k, dq, lens=lens, lim=(1, 0, 1), alpha=scale, split_k=sk, split_overwrite=True)
         # dK[key,d] = scale * sum_q dS[q,key] Q[q,d]
-        K.gemm(dP, qkv, dqkv, T, dh, T, T, C3, C3, False, False, b_off=0, c_off=C, nb0=B, nb1=H, sA=sP, sB=(T * C3, dh),
-               sC=(T * C3, dh), lens=lens, lim=(1, 0, 1), alpha=scale, split_k=sk, split_overwrite=True)
+        K.bgemm(dP.transpose(-1, -2), q, dk, lens=lens, lim=(1, 0, 1), alpha=scale, split_k=sk, split_overwrite=True)
         return dqkv, None, None
 
 
@@ -995,11 +996,10 @@ def mel_spectrogram(y, dft_basis, mel_basis_padded, n_fft, hop, n_mel, nbins, cl
     pad = n_fft // 2
     F = 1 + N // hop
     ypad = K.reflect_pad(y.contiguous(), pad)
-    W = ypad.shape[1]
     nre = dft_basis.shape[0]
     reim = torch.empty(B * F, nre, dtype=torch.float32, device=y.device)
-    K.gemm(ypad, dft_basis, reim, F, nre, n_fft, hop, n_fft, nre, True, True, nb0=B, nb1=1, sA=(W, 0), sB=(0, 0),
-           sC=(F * nre, 0))
+    frames = ypad.as_strided((B, F, n_fft), (ypad.shape[1], hop, 1))          # overlapping rows: frame f starts at sample f * hop
+    K.bgemm(frames, dft_basis.t().expand(B, n_fft, nre), reim.view(B, F, nre))
     ld_mag = mel_basis_padded.shape[1]
     mag, energy = K.stft_magnitude(reim, B * F, nbins, ld_mag)
     mel_fm = torch.empty(B * F, n_mel, dtype=torch.float32, device=y.device)
@@ -1133,17 +1133,18 @@ class _RelPosAttention(torch.autograd.Function):
     def forward(ctx, qu, qv, kv, pos, n_heads, scale, p_drop, seed, drop_offset):
         qu, qv, kv, pos = qu.contiguous(), qv.contiguous(), kv.contiguous(), pos.contiguous()
         B, T, C = qu.shape
-        dh = C // n_heads
         H = n_heads
-        sS = (H * T * T, T * T)
+        (quh,), (qvh,), (k, v) = _heads(qu, H), _heads(qv, H), _heads(kv, H, 2)
+        posh = _heads(pos.unsqueeze(0), H)[0].expand(B, -1, -1, -1)          # one table, shared by the batch
         S = torch.empty(B, H, T, T, dtype=torch.float32, device=qu.device)
         PS = torch.empty(B, H, T, T, dtype=torch.float32, device=qu.device)
-        K.gemm(qu, kv, S, T, T, dh, C, 2 * C, T, True, True, nb0=B, nb1=H, sA=(T * C, dh), sB=(T * 2 * C, dh), sC=sS)
-        K.gemm(qv, pos, PS, T, T, dh, C, C, T, True, True, nb0=B, nb1=H, sA=(T * C, dh), sB=(0, dh), sC=sS)
+        # S = QU K^T ; PS = QV pos^T (pos shared by the batch)
+        K.bgemm(quh, k.transpose(-1, -2), S)
+        K.bgemm(qvh, posh.transpose(-1, -2), PS)
         Pd = K.relpos_softmax_fwd(S, PS, T, scale, p_drop, seed, drop_offset, want_dropped=True)   # S <- P
         del PS
         out = torch.empty(B, T, C, dtype=torch.float32, device=qu.device)
-        K.gemm(Pd, kv, out, T, dh, T, T, 2 * C, C, True, False, b_off=C, nb0=B, nb1=H, sA=sS, sB=(T * 2 * C, dh), sC=(T * C, dh))
+        K.bgemm(Pd, v, _heads(out, H)[0])
         ctx.save_for_backward(qu, qv, kv, pos, S, seed)
         ctx.cfg = (n_heads, scale, p_drop, drop_offset)
         return out
@@ -1154,28 +1155,28 @@ class _RelPosAttention(torch.autograd.Function):
         H, scale, p_drop, drop_offset = ctx.cfg
         dO = dO.contiguous()
         B, T, C = qu.shape
-        dh = C // H
-        sS = (H * T * T, T * T)
         dkv = torch.empty_like(kv)
+        (quh,), (qvh,), (k, v), (dk, dv), (dOh,) = _heads(qu, H), _heads(qv, H), _heads(kv, H, 2), _heads(dkv, H, 2), _heads(dO, H)
+        posh = _heads(pos.unsqueeze(0), H)[0].expand(B, -1, -1, -1)
         # dV = Pd^T dO   (Pd regenerated from P and the counter-based mask)
         Pd = K.rowscale_dropout(P, None, p_drop, seed, drop_offset) if p_drop > 0 else P
-        K.gemm(Pd, dO, dkv, T, dh, T, T, C, 2 * C, False, False, c_off=C, nb0=B, nb1=H, sA=sS, sB=(T * C, dh), sC=(T * 2 * C, dh))
+        K.bgemm(Pd.transpose(-1, -2), dOh, dv)
         del Pd
         # dPd = dO V^T ; dS = P * (dP - sum dP P) * scale
         dS = torch.empty_like(P)
-        K.gemm(dO, kv, dS, T, T, dh, C, 2 * C, T, True, True, b_off=C, nb0=B, nb1=H, sA=(T * C, dh), sB=(T * 2 * C, dh), sC=sS)
+        K.bgemm(dOh, v.transpose(-1, -2), dS)
         K.relpos_softmax_bwd(P, dS, T, scale, p_drop, seed, drop_offset)
         # content path: dQU = dS K ; dK = dS^T QU
         dqu = torch.empty_like(qu)
-        K.gemm(dS, kv, dqu, T, dh, T, T, 2 * C, C, True, False, nb0=B, nb1=H, sA=sS, sB=(T * 2 * C, dh), sC=(T * C, dh))
-        K.gemm(dS, qu, dkv, T, dh, T, T, C, 2 * C, False, False, c_off=0, nb0=B, nb1=H, sA=sS, sB=(T * C, dh), sC=(T * 2 * C, dh))
+        K.bgemm(dS, k, _heads(dqu, H)[0])
+        K.bgemm(dS.transpose(-1, -2), quh, dk)
         # position path: dPS = unshift(dS) ; dQV = dPS pos ; dpos = sum_b dPS^T QV
         dPS = K.relshift_bwd(dS, T)
         del dS
         dqv = torch.empty_like(qv)
-        K.gemm(dPS, pos, dqv, T, dh, T, T, C, C, True, False, nb0=B, nb1=H, sA=sS, sB=(0, dh), sC=(T * C, dh))
+        K.bgemm(dPS, posh, _heads(dqv, H)[0])
         dpos_b = torch.empty(B, T, C, dtype=torch.float32, device=qu.device)
-        K.gemm(dPS, qv, dpos_b, T, dh, T, T, C, C, False, False, nb0=B, nb1=H, sA=sS, sB=(T * C, dh), sC=(T * C, dh))
+        K.bgemm(dPS.transpose(-1, -2), qvh, _heads(dpos_b, H)[0])
         dpos = K.colsum(dpos_b.view(dpos_b.shape[0], -1)).view(dpos_b.shape[1:])          # ordered sum over the batch (no torch reduction)
         return dqu, dqv, dkv, dpos, None, None, None, None, None
 
@@ -1243,7 +1244,7 @@ class _BmmNN(torch.autograd.Function):
         B, M, Kd = A.shape
         N = X.shape[2]
         out = torch.empty(B, M, N, dtype=torch.float32, device=A.device)
-        K.gemm(A, X, out, M, N, Kd, Kd, N, N, True, False, nb0=B, nb1=1, sA=(M * Kd, 0), sB=(Kd * N, 0), sC=(M * N, 0))
+        K.bgemm(A, X, out)
         ctx.save_for_backward(A, X)
         return out
 
@@ -1251,15 +1252,13 @@ class _BmmNN(torch.autograd.Function):
     def backward(ctx, dO):
         A, X = ctx.saved_tensors
         dO = dO.contiguous()
-        B, M, Kd = A.shape
-        N = X.shape[2]
         dA = dX = None
         if ctx.needs_input_grad[0]:
             dA = torch.empty_like(A)          # dA[m,k] = sum_n dO[m,n] X[k,n]
-            K.gemm(dO, X, dA, M, Kd, N, N, N, Kd, True, True, nb0=B, nb1=1, sA=(M * N, 0), sB=(Kd * N, 0), sC=(M * Kd, 0))
+            K.bgemm(dO, X.transpose(-1, -2), dA)
         if ctx.needs_input_grad[1]:
             dX = torch.empty_like(X)          # dX[k,n] = sum_m A[m,k] dO[m,n]
-            K.gemm(A, dO, dX, Kd, N, M, Kd, N, N, False, False, nb0=B, nb1=1, sA=(M * Kd, 0), sB=(M * N, 0), sC=(Kd * N, 0))
+            K.bgemm(A.transpose(-1, -2), dO, dX)
         return dA, dX
 
 
@@ -1297,7 +1296,7 @@ class _NegSqDist(torch.autograd.Function):
         gk = bmm_nn(g, with_ones(k))                                  # [B, Tq, C1]: g k | rowsum(g)
         dq = t2 * (q * gk[:, :, Cc:Cc + 1] - gk[:, :, :Cc])
         gtq = torch.empty(B, Tk, C1, dtype=torch.float32, device=g.device)
-        K.gemm(g, with_ones(q), gtq, Tk, C1, Tq, Tk, C1, C1, False, False, nb0=B, nb1=1, sA=(Tq * Tk, 0), sB=(Tq * C1, 0), sC=(Tk * C1, 0))
+        K.bgemm(g.transpose(-1, -2), with_ones(q), gtq)                # [B, Tk, C1]: g^T q | colsum(g)
         dk = t2 * (k * gtq[:, :, Cc:Cc + 1] - gtq[:, :, :Cc])
         return dq, dk, None
 
@@ -1359,10 +1358,11 @@ class _GRU(torch.autograd.Function):
         dgi, dgh, hprev = K.gru_bwd(dout.contiguous(), out, gates, whh, H, ndir, rev_mask)
         rows = B * T
         dwhh = torch.empty_like(whh)
+        dgh2, hprev2 = dgh.view(rows, ndir * 3 * H), hprev.view(rows, ndir * H)
         for d in range(ndir):              # dW_hh[d] = dgh_d^T h_prev_d : [3H, H], reduction over all B*T steps (split-K on MFMA)
-            K.gemm(dgh, hprev, dwhh, 3 * H, H, rows, ndir * 3 * H, ndir * H, H, False, False, a_off=d * 3 * H, b_off=d * H,
-                   c_off=d * 3 * H * H, split_k=max(2, _split_k_for(3 * H, H, rows)), split_overwrite=True)
-        dbhh = K.colsum(dgh.view(rows, ndir * 3 * H)).view(ndir, 3 * H)
+            K.bgemm(dgh2[:, d * 3 * H:(d + 1) * 3 * H].t(), hprev2[:, d * H:(d + 1) * H], dwhh[d],
+                    split_k=max(2, _split_k_for(3 * H, H, rows)), split_overwrite=True)
+        dbhh = K.colsum(dgh2).view(ndir, 3 * H)
         return dgi, dwhh, dbhh, None, None, None
 
 
@@ -1394,7 +1394,7 @@ class _BmmNT(torch.autograd.Function):
         B, M, Kd = A.shape
         N = Bm.shape[1]
         out = torch.empty(B, M, N, dtype=torch.float32, device=A.device)
-        K.gemm(A, Bm, out, M, N, Kd, Kd, Kd, N, True, True, nb0=B, nb1=1, sA=(M * Kd, 0), sB=(N * Kd, 0), sC=(M * N, 0), alpha=alpha)
+        K.bgemm(A, Bm.transpose(-1, -2), out, alpha=alpha)
         ctx.save_for_backward(A, Bm)
         ctx.alpha = alpha
         return out
@@ -1403,17 +1403,13 @@ class _BmmNT(torch.autograd.Function):
     def backward(ctx, dO):
         A, Bm = ctx.saved_tensors
         dO = dO.contiguous()
-        B, M, Kd = A.shape
-        N = Bm.shape[1]
         dA = dB = None
         if ctx.needs_input_grad[0]:        # dA[m,k] = alpha * sum_n dO[m,n] Bm[n,k]
             dA = torch.empty_like(A)
-            K.gemm(dO, Bm, dA, M, Kd, N, N, Kd, Kd, True, False, nb0=B, nb1=1, sA=(M * N, 0), sB=(N * Kd, 0), sC=(M * Kd, 0),
-                   alpha=ctx.alpha)
+            K.bgemm(dO, Bm, dA, alpha=ctx.alpha)
         if ctx.needs_input_grad[1]:        # dB[n,k] = alpha * sum_m dO[m,n] A[m,k]
             dB = torch.empty_like(Bm)
-            K.gemm(dO, A, dB, N, Kd, M, N, Kd, Kd, False, False, nb0=B, nb1=1, sA=(M * N, 0), sB=(M * Kd, 0), sC=(N * Kd, 0),
-                   alpha=ctx.alpha)
+            K.bgemm(dO.transpose(-1, -2), A, dB, alpha=ctx.alpha)
         return dA, dB, None
 
 
@@ -1671,7 +1667,7 @@ class _AddOverTime(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             ones = torch.ones(B, 1, T, dtype=torch.float32, device=g.device)
             dv = torch.empty(B, 1, Cc, dtype=torch.float32, device=g.device)
-            K.gemm(ones, g, dv, 1, Cc, T, T, Cc, Cc, True, False, nb0=B, nb1=1, sA=(T, 0), sB=(T * Cc, 0), sC=(Cc, 0))
+            K.bgemm(ones, g, dv)          # dv[b,0,c] = sum_t g[b,t,c]
         return (g if ctx.needs_input_grad[0] else None), dv
 
 
@@ -1743,19 +1739,17 @@ def bin_loss(hard, soft):
 
 # ---- Fastformer additive attention (csrc/fastformer.hip; reference fastformer.py FastAttention) ------------------------------------
 def _ff_linear(x, w, b, R=None):
-    M, Kd = x.shape
     N = w.shape[0]
-    out = torch.empty(M, N, dtype=torch.float32, device=x.device)
-    K.gemm(x, w, out, M, N, Kd, Kd, Kd, N, True, True, bias=b, R=R, ldr=N)
+    out = torch.empty(x.shape[0], N, dtype=torch.float32, device=x.device)
+    K.bgemm(x, w.t(), out, bias=b, R=R, ldr=N)
     return out
 
 
 def _ff_dgrad(dY, w, R=None):
     """dX = dY w (+ R)"""
-    M, N = dY.shape
     Kd = w.shape[1]
-    dX = torch.empty(M, Kd, dtype=torch.float32, device=dY.device)
-    K.gemm(dY, w, dX, M, Kd, N, N, Kd, Kd, True, False, R=R, ldr=Kd)
+    dX = torch.empty(dY.shape[0], Kd, dtype=torch.float32, device=dY.device)
+    K.bgemm(dY, w, dX, R=R, ldr=Kd)
     return dX
 
 

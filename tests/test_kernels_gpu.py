@@ -1507,3 +1507,54 @@ def test_pointer_vec_route_kinds_run_an_operand_beyond_the_buffer_window(kind, M
     print(f"{kind}: max |err| vs fp64 {err:.3e} (|ref| max {scale:.3e}, bound {bound:.3e}); bit-equal to {kind_c} on a compact copy: "
           f"{torch.equal(out, out_c)}")
     assert err <= bound, (err, bound)
+
+
+def _view_cases():
+    """name -> (base tensor shapes, lambda bases: (A, B, C) views): the layout classes of tests/test_gemm_views_cpu.py at B = 2, H = 2,
+    T = 37, d_h = 8 (no multiple of a tile, more than one batch of each level)"""
+    B, H, T, dh = 2, 2, 37, 8
+    Cc, C3, Hh, hop, nfft, nre, F = H * dh, 3 * H * dh, 8, 4, 16, 18, 9
+
+    def heads(x, parts=1):
+        return x.view(x.shape[0], x.shape[1], parts, H, dh).permute(2, 0, 3, 1, 4).unbind(0)
+    return {
+        "2d_rowA_colB": (dict(a=(T, 11), w=(13, 11), c=(T, 13)), lambda t: (t["a"], t["w"].t(), t["c"])),
+        "2d_colA_rowB": (dict(a=(11, T), b=(11, 13), c=(T, 13)), lambda t: (t["a"].t(), t["b"], t["c"])),
+        "3d": (dict(a=(B, T, 11), b=(B, 11, 13), c=(B, T, 13)), lambda t: (t["a"], t["b"], t["c"])),
+        "4d_QKt_offsets": (dict(qkv=(B, T, C3), c=(B, H, T, T)),
+                           lambda t: (heads(t["qkv"], 3)[0], heads(t["qkv"], 3)[1].transpose(-1, -2), t["c"])),
+        "4d_dV_into_a_slice": (dict(p=(B, H, T, T), do=(B, T, Cc), c=(B, T, C3)),
+                               lambda t: (t["p"].transpose(-1, -2), heads(t["do"])[0], heads(t["c"], 3)[2])),
+        "4d_dK_into_a_slice": (dict(p=(B, H, T, T), qkv=(B, T, C3), c=(B, T, C3)),
+                               lambda t: (t["p"].transpose(-1, -2), heads(t["qkv"], 3)[0], heads(t["c"], 3)[1])),
+        "expanded_batch": (dict(qv=(B, T, Cc), pos=(T, Cc), c=(B, H, T, T)),
+                           lambda t: (heads(t["qv"])[0], heads(t["pos"].unsqueeze(0))[0].expand(B, H, T, dh).transpose(-1, -2), t["c"])),
+        "size1_M": (dict(a=(B, 1, T), g=(B, T, Cc), c=(B, 1, Cc)), lambda t: (t["a"], t["g"], t["c"])),
+        "2d_column_slices": (dict(dgh=(B * T, 2 * 3 * Hh), hp=(B * T, 2 * Hh), c=(2, 3 * Hh, Hh)),
+                             lambda t: (t["dgh"][:, 3 * Hh:].t(), t["hp"][:, Hh:], t["c"][1])),
+        "as_strided_frames": (dict(y=(B, (F - 1) * hop + nfft), basis=(nre, nfft), c=(B * F, nre)),
+                              lambda t: (t["y"].as_strided((B, F, nfft), ((F - 1) * hop + nfft, hop, 1)),
+                                         t["basis"].t().expand(B, nfft, nre), t["c"].view(B, F, nre))),
+    }
+
+
+@pytest.mark.parametrize("case", list(_view_cases()))
+def test_bgemm_on_views_equals_float64_einsum_and_writes_only_the_view(case):
+    """kernels.bgemm on device views of every layout class.  Operands are integers in [-64, 64] and K <= 74: every product and partial
+    sum is an integer below 2^19, exact in fp32 on every kernel family, so the result EQUALS the float64 einsum of the views; the
+    output's base tensor starts as NaN and is still NaN wherever the view does not reach."""
+    shapes, views = _view_cases()[case]
+    g = torch.Generator().manual_seed(len(case))
+    host = {n: torch.randint(-64, 65, s, generator=g).float() for n, s in shapes.items()}
+    host["c"] = torch.full(shapes["c"], float("nan"))
+    dev = {n: t.to(DEV) for n, t in host.items()}
+    A, Bv, Cv = views(dev)
+    assert K.bgemm(A, Bv, Cv) is Cv
+    torch.cuda.synchronize()
+    hA, hB, _ = views(host)
+    ref = torch.einsum("...mk,...kn->...mn", hA.double(), hB.double())
+    got = dev["c"].cpu()
+    written = torch.zeros(shapes["c"], dtype=torch.bool)
+    views(dict(host, c=written))[2].fill_(True)
+    assert torch.equal(views(dict(host, c=got))[2].double(), ref.expand(Cv.shape))
+    assert ref.abs().max() > 0 and bool(torch.isnan(got[~written]).all()) and int(written.sum()) == Cv.numel()
