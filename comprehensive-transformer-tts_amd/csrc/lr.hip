@@ -25,16 +25,28 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
   return v;
 }
 
+__device__ __forceinline__ long long wave_incl_scan64(long long v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    long long t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
 // one block per batch row.  Phase 1 (wave 0): scan durations -> cum (LDS + global).
 // Phase 2 (all threads): upper-bound search of t in cum -> mel2ph.
+// Every duration is capped at 2e9 and Ts <= 15000, so a prefix is at most 3e13: the scan runs in 64 bits and cannot wrap.  mel_len gets
+// the exact total; s_cum / cum hold min(prefix, INT32_MAX), still non-decreasing, and the search only asks cum > t for t < Tm <= INT32_MAX,
+// which saturation does not change.
 __global__ __launch_bounds__(256) void lr_index_kernel(const void* dur, int dur_is_float, int round_mode,
                                                         const uint8_t* pad, int Ts, int Tm, int32_t* mel2ph,
                                                         int64_t* mel_len, int32_t* cum_out) {
   extern __shared__ int s_cum[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  __shared__ int s_total;
+  __shared__ long long s_total;
   if (tid < 64) {
-    int carry = 0;
+    long long carry = 0;
     for (int i0 = 0; i0 < Ts; i0 += 64) {
       const int i = i0 + lane;
       int dv = 0;
@@ -49,10 +61,11 @@ __global__ __launch_bounds__(256) void lr_index_kernel(const void* dur, int dur_
         }
         if (pad && pad[(long)b * Ts + i]) dv = 0;
       }
-      int inc = wave_incl_scan(dv, lane) + carry;
+      const long long inc = wave_incl_scan64(dv, lane) + carry;
       if (i < Ts) {
-        s_cum[i] = inc;
-        if (cum_out) cum_out[(long)b * Ts + i] = inc;
+        const int sat = (int)min(inc, (long long)INT32_MAX);
+        s_cum[i] = sat;
+        if (cum_out) cum_out[(long)b * Ts + i] = sat;
       }
       carry = __shfl(inc, 63, 64);
     }
@@ -63,7 +76,7 @@ __global__ __launch_bounds__(256) void lr_index_kernel(const void* dur, int dur_
   }
   __syncthreads();
   if (!mel2ph) return;
-  const int total = s_total;
+  const long long total = s_total;
   for (int t = tid; t < Tm; t += 256) {
     int v = 0;
     if (t < total) {

@@ -274,6 +274,10 @@ int ctts_conv_weight_repack(const float* src, float* dst, int cout, int cin, int
  *   mel2ph[b,t] = 1 + #{i : cum[i] <= t} for t < min(total, Tm) else 0;  mel_len[b] = total
  *   (un-cropped).  dur_is_float selects float32 vs int64 input; round_mode 0 = trunc (LR),
  *   1 = round-half-even (dur_to_mel2ph); pad[b,i] != 0 zeroes that duration (dur_padding).
+ *   A duration <= 0, -0.0 or NaN counts 0; one above 2e9 (+inf included) counts 2e9.  The prefix sums are
+ *   taken in 64 bits and never wrap: mel_len[b] is the exact total (up to Ts * 2e9), cum[b,i] =
+ *   min(prefix_i, INT32_MAX), and mel2ph follows the exact prefixes (t < Tm <= INT32_MAX, so the
+ *   saturation of cum does not change it).
  * ctts_lr_gather_fwd: out[b,t,:] = x[b, mel2ph[b,t]-1, :] or 0.      (expand + pad/crop)
  * ctts_lr_gather_bwd: dx[b,i,:] = sum over the contiguous frame run of phoneme i of dy.   */
 int ctts_lr_index(const void* dur, int dur_is_float, int round_mode, const uint8_t* pad, int B, int Ts, int Tm,

@@ -16,6 +16,14 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
+def _assert_restated_mask(mask, p, seed, off):
+    """a mask drawn from K.rowscale_dropout(ones) is also the independent model's (tests/glue_restate64.drop_scale over keep_mask)"""
+    from tests import glue_restate64 as G
+    rows, C = mask.shape
+    want = G.drop_scale(int(seed.item()) & 0xFFFFFFFFFFFFFFFF, off, p, rows, C, torch.float32)
+    assert torch.equal(mask.float().cpu(), want), "the kernel-drawn dropout mask differs from the restated mask"
+
+
 def rnd(*shape, seed=0, scale=1.0):
     g = torch.Generator().manual_seed(seed + sum(shape))
     return (torch.rand(*shape, generator=g) * 2 - 1) * scale
@@ -603,6 +611,7 @@ def test_dominant_stream_k_kernel_vs_fp64_at_the_bench_shape():
     torch.cuda.synchronize()
     assert _sk_error_word() == 0
     mask = K.rowscale_dropout(torch.ones(M, N, device=DEV), None, p, seed, off).view(B, T, N)        # 0 or 1/(1-p), from (seed, offset, m*N+n)
+    _assert_restated_mask(mask.view(M, N), p, seed, off)
     xd, wd = x.double().cpu(), w.double().cpu().view(N, ks, Cin)
     worst_c = worst_z = 0.0
     for b in range(B):
@@ -1074,6 +1083,7 @@ def test_gemm_lean_epilogue_modes_vs_fp64(mode, M, N, Kd, pad):
     mask = torch.ones(M, N, dtype=torch.float64, device=DEV)
     if drop:
         mask = K.rowscale_dropout(torch.ones(M, N, device=DEV), None, p, seed, off).double()       # 0 or 1/(1-p)
+        _assert_restated_mask(mask, p, seed, off)
     acc = A.double() @ B.double().t()
     if not bwd:
         Zb = torch.full((M + 3, ld), float("nan"), device=DEV) if act else None
@@ -1202,6 +1212,7 @@ def test_positional_embedding_add_fwd_bwd(B, T, C, p, use_alpha, use_mask):
     mask = torch.ones(B * T, C, device=DEV)
     if p > 0:
         mask = K.rowscale_dropout(torch.ones(B * T, C, device=DEV), None, p, drop.seed, 1)        # the op drew call-site offset 1
+        _assert_restated_mask(mask, p, drop.seed, 1)
     mask = mask.view(B, T, C)
     pe = torch.nn.functional.embedding(pos.long(), table)
     a32 = alpha.detach() if use_alpha else torch.ones(1, device=DEV)
