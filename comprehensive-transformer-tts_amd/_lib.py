@@ -214,6 +214,9 @@ _SIGNATURES = {
     "ctts_mel_cepstrum": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "ctts_dtw": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "ctts_path_metrics": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "ctts_resample": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "ctts_peak_normalize": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _f32, _vp],
+    "ctts_resample_tile": [C.c_int, C.c_int, C.c_int, C.c_int],
     "ctts_comm_unique_id": [_vp],
     "ctts_comm_create": [C.POINTER(_vp), _i32, _i32, _vp],
     "ctts_comm_destroy": [_vp],

@@ -1877,3 +1877,81 @@ def path_metrics(path, path_len, f0_x, f0_y):
     _lib.check(_lib.load().ctts_path_metrics(_p(path), _p(path_len), _p(f0_x), _p(f0_y), _p(out), B, f0_x.shape[1], f0_y.shape[1], P, _stream()),
                "ctts_path_metrics")
     return out
+
+
+# ---- audio resampling and peak normalisation (csrc/resample.hip) -------------------------------------------------------------------
+RESAMPLE_MAX_RATIO_TERM = 1024        # L, M after reduction
+RESAMPLE_MAX_PHASE_TAPS = 1024        # T
+RESAMPLE_TAP_GRANULE = 8              # T is a multiple of this: the kernel loads eight coefficients at a time
+RESAMPLE_MAX_SAMPLES = 1 << 30        # per row, on either side
+
+
+def resample_tile(L, M, T, half):
+    """Consecutive outputs one tile of the resampling kernel covers for these parameters (a multiple of L; 0 for L == M or parameters
+    the kernel refuses).  It depends on (L, M, T, half) alone."""
+    return int(_lib.load().ctts_resample_tile(int(L), int(M), int(T), int(half)))
+
+
+def resample(wav, lens, bank, L, M, half):
+    """wav [B,N] float32, lens int32 [B], bank [L,T] float32 (None when L == M) -> (out [B, ceil(N L / M)], out_lens int32 [B]):
+    out[b][n] = sum_j bank[(n M + half) mod L][j] wav[b][(n M + half) div L - j] over the row's own lens[b] samples"""
+    if not torch.is_tensor(wav) or wav.dim() != 2:
+        raise _lib.CttsError("resample: expected wav [B, N]")
+    _p(wav)
+    _al4(_f32c(wav, "wav"), "wav")
+    B, N = wav.shape
+    L, M, half = int(L), int(M), int(half)
+    if B < 1 or N < 1:
+        raise _lib.CttsError(f"resample: empty batch {tuple(wav.shape)}")
+    if B > 65535:
+        raise _lib.CttsError(f"resample: at most 65535 utterances per call, got {B}")
+    if not (1 <= L <= RESAMPLE_MAX_RATIO_TERM and 1 <= M <= RESAMPLE_MAX_RATIO_TERM):
+        raise _lib.CttsError(f"resample: the reduced ratio {L}/{M} has a term outside [1, {RESAMPLE_MAX_RATIO_TERM}]")
+    No = (N * L + M - 1) // M
+    if N > RESAMPLE_MAX_SAMPLES or No > RESAMPLE_MAX_SAMPLES:
+        raise _lib.CttsError(f"resample: {N} -> {No} samples per row exceed 2^30")
+    _lens_i32(lens, B, "resample")
+    T = 0
+    if L != M:
+        if not torch.is_tensor(bank) or bank.dim() != 2 or bank.shape[0] != L:
+            raise _lib.CttsError(f"resample: expected bank [L = {L}, T]")
+        _p(bank)
+        _f32c(bank, "bank")
+        T = bank.shape[1]
+        if T % RESAMPLE_TAP_GRANULE or not RESAMPLE_TAP_GRANULE <= T <= RESAMPLE_MAX_PHASE_TAPS:
+            raise _lib.CttsError(f"resample: T = {T} must be a multiple of {RESAMPLE_TAP_GRANULE} in [{RESAMPLE_TAP_GRANULE}, {RESAMPLE_MAX_PHASE_TAPS}]")
+        if half < 0 or 2 * half + 1 > L * T:
+            raise _lib.CttsError(f"resample: a bank [{L}, {T}] does not hold 2 * {half} + 1 taps")
+        if bank.data_ptr() % 32:
+            raise _lib.CttsError("resample: bank must be 32-byte aligned")
+    out = torch.empty(B, No, dtype=torch.float32, device=wav.device)
+    out_lens = torch.empty(B, dtype=torch.int32, device=wav.device)
+    _lib.check(_lib.load().ctts_resample(_p(wav), _p(lens), _p(bank) if L != M else None, _p(out), _p(out_lens), B, N, L, M, T, half, _stream()),
+               "ctts_resample")
+    return out, out_lens
+
+
+def peak_normalize(wav, lens, max_wav_value=32768.0, return_int16=False):
+    """wav [B,N] float32, lens int32 [B] -> (out float32 [B,N] = trunc(wav / peak * max_wav_value) saturated to int16, over 32768;
+    int16 [B,N] or None; peak [B]; valid int32 [B])"""
+    if not torch.is_tensor(wav) or wav.dim() != 2:
+        raise _lib.CttsError("peak_normalize: expected wav [B, N]")
+    _p(wav)
+    _al4(_f32c(wav, "wav"), "wav")
+    B, N = wav.shape
+    if B < 1 or N < 1:
+        raise _lib.CttsError(f"peak_normalize: empty batch {tuple(wav.shape)}")
+    if B > 65535:
+        raise _lib.CttsError(f"peak_normalize: at most 65535 utterances per call, got {B}")
+    mwv = float(max_wav_value)
+    if not (0.0 < mwv < float("inf")):
+        raise _lib.CttsError(f"peak_normalize: max_wav_value must be positive and finite, got {max_wav_value}")
+    _lens_i32(lens, B, "peak_normalize")
+    dev = wav.device
+    out = torch.empty_like(wav)
+    q16 = torch.empty(B, N, dtype=torch.int16, device=dev) if return_int16 else None
+    peak = torch.empty(B, dtype=torch.float32, device=dev)
+    valid = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().ctts_peak_normalize(_p(wav), _p(lens), _p(out), _p(q16), _p(peak), _p(valid), B, N, mwv, _stream()),
+               "ctts_peak_normalize")
+    return out, q16, peak, valid

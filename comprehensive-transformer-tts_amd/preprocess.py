@@ -194,11 +194,28 @@ class DatasetStats:
         return out
 
 
-def process_batch(wavs, n_phones, stft, preprocess_config, spans=None):
+def _to_stft_rate(wavs, source_rate, target_rate, quality):
+    """the utterances as one ragged batch through `resample.resample` (librosa.load(path, sampling_rate) of :364); lengths stay on the host"""
+    from . import resample as RS
+    lens = [int(w.numel()) for w in wavs]
+    if min(lens) < 1:
+        raise ValueError("process_batch: empty utterance")
+    wav = torch.zeros(len(wavs), max(lens), dtype=torch.float32, device=wavs[0].device)
+    for i, w in enumerate(wavs):
+        wav[i, :lens[i]] = w
+    out, _ = RS.resample(wav, lens, source_rate, target_rate, quality)
+    g = math.gcd(int(source_rate), int(target_rate))
+    L, M = int(target_rate) // g, int(source_rate) // g
+    return [out[i, :RS.output_length(n, L, M)] for i, n in enumerate(lens)]
+
+
+def process_batch(wavs, n_phones, stft, preprocess_config, spans=None, source_rate=None, resample_quality="kaiser_best"):
     """One ragged batch through the unsupervised branch of `Preprocessor.process_utterance` (:375-446).
-    wavs: sequence of 1-D float device tensors (raw audio at the STFT's sampling rate); n_phones: phonemes per utterance (host ints);
-    stft: the `TacotronSTFT` (FFT path, on the device); spans: optional [B,2] host ints `[start, end)` in samples that REPLACE the trim
-    (the supervised branch cuts by TextGrid times, parsed on the host).
+    wavs: sequence of 1-D float device tensors (raw audio at the STFT's sampling rate, or at `source_rate`); n_phones: phonemes per
+    utterance (host ints); stft: the `TacotronSTFT` (FFT path, on the device); spans: optional [B,2] host ints `[start, end)` in samples
+    that REPLACE the trim (the supervised branch cuts by TextGrid times, parsed on the host).
+    source_rate: the sampling rate of `wavs` when it is not the STFT's: the utterances are first resampled to `stft.sampling_rate` as one
+    ragged batch (`resample.resample` with `resample_quality`), and everything below - `spans`, start, end - is in target-rate samples.
     Chain: trim kernel -> the ragged mel / energy kernel on the trimmed spans -> `pitch_targets_from_wav` on the same spans -> prior
     kernel; every output is cut to `duration` = (end - start) // hop frames like :389-400.  Returns one dict of numpy arrays per
     utterance: mel [T,n_mel], energy [T], f0 [T] (Hz), pitch [T] (coarse ids), cwt_spec [T,10], f0cwt_mean_std [2], attn_prior
@@ -218,6 +235,8 @@ def process_batch(wavs, n_phones, stft, preprocess_config, spans=None):
     nph = [int(n) for n in n_phones]
     if len(nph) != B or min(nph) < 1:
         raise ValueError(f"process_batch: need one positive phoneme count per utterance, got {nph}")
+    if source_rate is not None and int(source_rate) != int(stft.sampling_rate):
+        wavs = _to_stft_rate(wavs, source_rate, stft.sampling_rate, resample_quality)
     if stft._dft_basis.device != dev:
         stft.to(dev)
     pp = preprocess_config["preprocessing"]

@@ -877,6 +877,38 @@ int ctts_dtw(const float* x, const float* y, const int32_t* x_lens, const int32_
 int ctts_path_metrics(const int32_t* path, const int32_t* path_len, const float* f0_x, const float* f0_y, double* out, int B, int Tx, int Ty,
                       int P, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Audio resampling on the device (csrc/resample.hip): the band-limited rate change behind every
+ * librosa.load(path, sampling_rate) of the reference (preprocessor.py:364, :460, vctk.py:31) and the peak normalisation + int16 cast of
+ * prepare_align (vctk.py:32-36).  fp32 data, lengths are int32 device arrays clamped to [0, N] in the kernels; stream-ordered, no
+ * allocation, no host sync, no float atomics: bit-reproducible run to run, and a row's result does not depend on B, on the other rows
+ * or on the launch geometry.
+ *
+ * ctts_resample: exact-phase polyphase FIR for the reduced ratio L / M (L up, M down).  wav [B][N], lens [B], bank [L][T] ->
+ * out [B][No], No = ceil(N L / M), out_lens [B] = ceil(lens[b] L / M).  With t = n M + half, r = t mod L, k = t div L:
+ *   out[b][n] = sum_{j = 0 .. T-1} bank[r][j] x_b[k - j],   x_b[i] = wav[b][i] for 0 <= i < lens[b], 0 elsewhere,
+ * accumulated in fp32 with fmaf in the order j = 0, 1, .. T-1.  For a prototype filter h of 2 half + 1 taps the caller fills
+ * bank[r][j] = h[r + j L] (0 beyond the last tap), which makes this out[n] = sum_k h[n M + half - k L] x[k]: PARITY with librosa /
+ * resampy is UNPINNED (neither is installed where this project is built; resampy interpolates a filter table, this is exact-phase).
+ *   EVERY element of out is written; columns at and beyond out_lens[b] are exactly 0.  Samples at and beyond lens[b] are never read.
+ *   L == M copies (bank may be NULL, T and half are ignored).
+ *   DOMAIN (refused before any launch, never truncated): 1 <= L, M <= 1024; T a multiple of 8 with 8 <= T <= 1024 and
+ *   L T >= 2 half + 1; bank 32-byte aligned; B <= 65535; 1 <= N and No <= 2^30 (positions are formed in 64 bits).
+ *   ctts_resample_tile(L, M, T, half): the number of consecutive outputs one tile of the kernel covers for these parameters (a
+ *   multiple of L; 0 for L == M or parameters outside the domain) - it depends on nothing else, tests stand on its edges.
+ *
+ * ctts_peak_normalize: per utterance b, peak[b] = max |wav[b][i]| over i < lens[b];  v = (wav[b][i] / peak[b]) * max_wav_value as numpy
+ * evaluates it on a float32 array (an IEEE division, then one multiply: two roundings);  q = trunc(v) saturated to [-32768, 32767];
+ * out[b][i] = q / 32768 (what reading the written 16-bit file back gives), out_i16[b][i] = q (NULL: not wanted), 0 at and beyond
+ * lens[b] - every element is written.  ONE deviation: the reference casts v = +32768.0 to int16, which is undefined in C and wraps to
+ * -32768 on x86; here it saturates to 32767.  peak[b] == 0 (or lens[b] <= 0) gives zeros and valid[b] = 0 where the reference divides
+ * by zero; valid[b] = 1 otherwise.  DOMAIN: finite samples, max_wav_value > 0, B <= 65535, N >= 1. */
+int ctts_resample_tile(int L, int M, int T, int half);
+int ctts_resample(const float* wav, const int32_t* lens, const float* bank, float* out, int32_t* out_lens, int B, int N, int L, int M, int T,
+                  int half, void* stream);
+int ctts_peak_normalize(const float* wav, const int32_t* lens, float* out, int16_t* out_i16, float* peak, int32_t* valid, int B, int N,
+                        float max_wav_value, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
