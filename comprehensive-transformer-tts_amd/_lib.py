@@ -217,6 +217,14 @@ _SIGNATURES = {
     "ctts_resample": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "ctts_peak_normalize": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _f32, _vp],
     "ctts_resample_tile": [C.c_int, C.c_int, C.c_int, C.c_int],
+    "ctts_loudness_chunk": [],
+    "ctts_loudness_tile_slots": [],
+    "ctts_loudness_coef_doubles": [],
+    "ctts_loudness_max_segments": [],
+    "ctts_kweight_energy": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
+    "ctts_loudness_gate": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                           C.c_double, C.c_int, _vp],
+    "ctts_apply_gain": [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp],
     "ctts_comm_unique_id": [_vp],
     "ctts_comm_create": [C.POINTER(_vp), _i32, _i32, _vp],
     "ctts_comm_destroy": [_vp],
@@ -228,7 +236,7 @@ EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["ctts_last_error", "ctts_version"
                                                "ctts_workspace_error_word", "ctts_fastformer_workspace_floats",
                                                "ctts_griffinlim_workspace_bytes", "ctts_griffinlim_state_floats",
                                                "ctts_pitch_track_workspace_bytes", "ctts_trim_silence_workspace_bytes",
-                                               "ctts_dtw_workspace_bytes"])
+                                               "ctts_dtw_workspace_bytes", "ctts_loudness_workspace_bytes"])
 ADAM_STATE_FLOATS = 3 + 2048          # CTTS_ADAM_STATE_FLOATS of include/ctts.h
 ABI_VERSION = 2                       # ctts_version() of the library this binding was written for
 
@@ -283,6 +291,8 @@ def load():
     lib.ctts_trim_silence_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ctts_dtw_workspace_bytes.restype = C.c_size_t
     lib.ctts_dtw_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.ctts_loudness_workspace_bytes.restype = C.c_size_t
+    lib.ctts_loudness_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.ctts_relmha_workspace_floats.restype = C.c_size_t
     lib.ctts_relmha_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int]
     _lib = lib

@@ -1955,3 +1955,114 @@ def peak_normalize(wav, lens, max_wav_value=32768.0, return_int16=False):
     _lib.check(_lib.load().ctts_peak_normalize(_p(wav), _p(lens), _p(out), _p(q16), _p(peak), _p(valid), B, N, mwv, _stream()),
                "ctts_peak_normalize")
     return out, q16, peak, valid
+
+
+# ---- loudness metering and normalisation (csrc/loudness.hip) -----------------------------------------------------------------------
+LOUDNESS_MAX_SAMPLES = 1 << 24        # per row
+
+
+def loudness_chunk():
+    """samples one lane of the K-weighting kernels filters: utterances are chained in chunks of this many samples from their sample 0"""
+    return int(_lib.load().ctts_loudness_chunk())
+
+
+def loudness_limits():
+    """-> (hop segments a 64-chunk tile may touch, float64 words of the coefficient buffer, blocks / segments the gate holds)"""
+    lib = _lib.load()
+    return int(lib.ctts_loudness_tile_slots()), int(lib.ctts_loudness_coef_doubles()), int(lib.ctts_loudness_max_segments())
+
+
+def _loudness_batch(wav, lens, what):
+    if not torch.is_tensor(wav) or wav.dim() != 2:
+        raise _lib.CttsError(f"{what}: expected wav [B, N]")
+    _p(wav)
+    _al4(_f32c(wav, "wav"), "wav")
+    B, N = wav.shape
+    if B < 1 or N < 1:
+        raise _lib.CttsError(f"{what}: empty batch {tuple(wav.shape)}")
+    if B > 65535 or N > LOUDNESS_MAX_SAMPLES:
+        raise _lib.CttsError(f"{what}: at most 65535 utterances of 2^24 samples per call, got {B} x {N}")
+    _lens_i32(lens, B, what)
+    return B, N
+
+
+def _loudness_tables(edges, chunk_seg, N, what):
+    for t, name in ((edges, "edges"), (chunk_seg, "chunk_seg")):
+        _p(t)
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise _lib.CttsError(f"{what}: {name} must be a contiguous 1-D int32 device tensor")
+    tile = 64 * loudness_chunk()
+    if edges.numel() < 2 or chunk_seg.numel() < (N + tile - 1) // tile * 64:
+        raise _lib.CttsError(f"{what}: the segment tables do not cover {N} samples")
+
+
+def kweight_energy(wav, lens, coef, edges, chunk_seg):
+    """wav [B,N] float32, lens int32 [B], coef float64 (biquads + state-transition powers), edges / chunk_seg int32 (include/ctts.h) ->
+    (hop_sums float64 [B, tiles, slots]: sum of squares of the K-weighted signal per 64-chunk tile and hop segment, zero where a tile
+    lies beyond its utterance; peak float32 [B] = max |wav|)"""
+    B, N = _loudness_batch(wav, lens, "kweight_energy")
+    slots, ncoef, _ = loudness_limits()
+    _p(coef)
+    if coef.dtype != torch.float64 or not coef.is_contiguous() or coef.numel() != ncoef:
+        raise _lib.CttsError(f"kweight_energy: coef must be {ncoef} contiguous float64 words")
+    _loudness_tables(edges, chunk_seg, N, "kweight_energy")
+    lib = _lib.load()
+    dev = wav.device
+    tile = 64 * loudness_chunk()
+    ws = torch.empty(lib.ctts_loudness_workspace_bytes(B, N) // 8, dtype=torch.float64, device=dev)
+    hop_sums = torch.zeros(B, (N + tile - 1) // tile, slots, dtype=torch.float64, device=dev)
+    peak = torch.empty(B, dtype=torch.float32, device=dev)
+    _lib.check(lib.ctts_kweight_energy(_p(wav), _p(lens), _p(coef), _p(edges), _p(chunk_seg), _p(hop_sums), _p(peak), B, N, edges.numel(),
+                                       chunk_seg.numel(), _p(ws), _stream()), "ctts_kweight_energy")
+    return hop_sums, peak
+
+
+def loudness_gate(hop_sums, lens, n_blocks, edges, chunk_seg, blocks, peak, N, block_samples, target=-22.0, peak_limit=True, curve=False):
+    """hop_sums / peak of `kweight_energy`, n_blocks int32 [B], blocks int32 [J,2] -> (loudness float64 [B], gain float32 [B],
+    valid int32 [B], curve float64 [B,J] or None)"""
+    if not torch.is_tensor(hop_sums) or hop_sums.dim() != 3 or hop_sums.dtype != torch.float64 or not hop_sums.is_contiguous():
+        raise _lib.CttsError("loudness_gate: expected hop_sums float64 [B, tiles, slots]")
+    _p(hop_sums)
+    B = hop_sums.shape[0]
+    N = int(N)
+    slots, _, max_segs = loudness_limits()
+    tile = 64 * loudness_chunk()
+    if hop_sums.shape[1] != (N + tile - 1) // tile or hop_sums.shape[2] != slots:
+        raise _lib.CttsError(f"loudness_gate: hop_sums {tuple(hop_sums.shape)} does not belong to rows of {N} samples")
+    _lens_i32(lens, B, "loudness_gate")
+    _lens_i32(n_blocks, B, "loudness_gate n_blocks")
+    _loudness_tables(edges, chunk_seg, N, "loudness_gate")
+    _p(blocks)
+    if blocks.dtype != torch.int32 or blocks.dim() != 2 or blocks.shape[1] != 2 or not blocks.is_contiguous() or blocks.shape[0] < 1:
+        raise _lib.CttsError("loudness_gate: blocks must be a contiguous int32 [J, 2] device tensor")
+    J = blocks.shape[0]
+    if J > max_segs or edges.numel() - 2 > max_segs:
+        raise _lib.CttsError(f"loudness_gate: at most {max_segs} blocks and hop segments per utterance, got {J} / {edges.numel() - 2}")
+    _p(peak)
+    if peak.dtype != torch.float32 or peak.numel() != B:
+        raise _lib.CttsError("loudness_gate: peak must be float32 [B]")
+    dev = hop_sums.device
+    loud = torch.empty(B, dtype=torch.float64, device=dev)
+    gain = torch.empty(B, dtype=torch.float32, device=dev)
+    valid = torch.empty(B, dtype=torch.int32, device=dev)
+    cur = torch.empty(B, J, dtype=torch.float64, device=dev) if curve else None
+    _lib.check(_lib.load().ctts_loudness_gate(_p(hop_sums), _p(lens), _p(n_blocks), _p(edges), _p(chunk_seg), _p(blocks), _p(peak), _p(loud),
+                                              _p(gain), _p(valid), _p(cur), B, N, edges.numel(), chunk_seg.numel(), J, float(block_samples),
+                                              float(target), 1 if peak_limit else 0, _stream()), "ctts_loudness_gate")
+    return loud, gain, valid, cur
+
+
+def apply_gain(wav, lens, gain, out=None):
+    """out[b][i] = wav[b][i] * gain[b] for i < lens[b], 0 beyond; `out` may be `wav`"""
+    B, N = _loudness_batch(wav, lens, "apply_gain")
+    _p(gain)
+    if gain.dtype != torch.float32 or gain.numel() != B or not gain.is_contiguous():
+        raise _lib.CttsError("apply_gain: gain must be float32 [B]")
+    if out is None:
+        out = torch.empty_like(wav)
+    else:
+        _p(out)
+        if _f32c(out, "out").shape != wav.shape:
+            raise _lib.CttsError(f"apply_gain: out {tuple(out.shape)} does not match wav {tuple(wav.shape)}")
+    _lib.check(_lib.load().ctts_apply_gain(_p(wav), _p(lens), _p(gain), _p(out), B, N, _stream()), "ctts_apply_gain")
+    return out

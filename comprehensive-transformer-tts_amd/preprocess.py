@@ -280,3 +280,29 @@ def process_batch(wavs, n_phones, stft, preprocess_config, spans=None, source_ra
                     "attn_prior": prior[b, :nph[b], :T].copy(), "duration": T, "start": int(start[b]), "end": int(end[b]),
                     "valid": int(valid[b])})
     return out
+
+
+def process_batch_loudness(wavs, n_phones, stft, preprocess_config, loudness=-22.0, spans=None, source_rate=None,
+                           resample_quality="kaiser_best"):
+    """`process_batch` on loudness-normalised audio, the order of the reference's `get_mel_from_wav` path with pyloudnorm
+    (audio/stft.py:226-231): the utterances are resampled to the STFT's rate when `source_rate` says so, each is brought to `loudness`
+    LUFS (ITU-R BS.1770 integrated loudness, `loudness.normalize_loudness` with the reference's peak guard) as one ragged batch on the
+    device, and the result goes through `process_batch` unchanged.  The trim threshold is relative to the utterance's own loudest frame,
+    so the trimmed spans are those of the unnormalised audio up to the rounding of one fp32 product per sample.  Every utterance must
+    be at least 0.4 s long at the STFT's rate.  `process_batch` itself keeps its parameter list: earlier callers and tests pin it."""
+    from .loudness import normalize_loudness
+    if len(wavs) == 0:
+        raise ValueError("process_batch_loudness: empty batch")
+    for w in wavs:
+        if not torch.is_tensor(w) or not w.is_cuda:
+            raise CttsError("process_batch_loudness computes on the MI355X: pass device tensors - no CPU fallback exists")
+        if w.dim() != 1:
+            raise ValueError(f"process_batch_loudness: each utterance is a 1-D tensor, got {tuple(w.shape)}")
+    if source_rate is not None and int(source_rate) != int(stft.sampling_rate):
+        wavs = _to_stft_rate(wavs, source_rate, stft.sampling_rate, resample_quality)
+    lens = [int(w.numel()) for w in wavs]
+    wav = torch.zeros(len(wavs), max(lens), dtype=torch.float32, device=wavs[0].device)
+    for i, w in enumerate(wavs):
+        wav[i, :lens[i]] = w
+    out = normalize_loudness(wav, lens, stft.sampling_rate, target=float(loudness), peak_limit=True, out=wav)[0]
+    return process_batch([out[i, :n] for i, n in enumerate(lens)], n_phones, stft, preprocess_config, spans=spans)

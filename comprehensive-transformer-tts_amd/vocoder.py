@@ -284,3 +284,19 @@ def infer_wavs(vocoder, mels, mel_lens, max_wav_value=32768.0):
     lens = mel_lens.tolist() if torch.is_tensor(mel_lens) else [int(v) for v in mel_lens]
     wavs = (wavs.cpu().numpy() * max_wav_value).astype("int16")
     return [wavs[i][: hop * max(0, min(int(n), mels.shape[2]))] for i, n in enumerate(lens)]
+
+
+def infer_wavs_loudness(vocoder, mels, mel_lens, loudness=-22.0, sampling_rate=22050, max_wav_value=32768.0):
+    """`infer_wavs` with every utterance delivered at `loudness` LUFS: the ragged generator output is brought to that ITU-R BS.1770
+    integrated loudness on the device, at `sampling_rate` (`loudness.normalize_loudness` with peak_limit=True: an utterance that would
+    clip is scaled to a peak of 1 instead), before the int16 cast on the host.  Every utterance must be at least 0.4 s long.
+    `infer_wavs` itself keeps its parameter list: earlier callers and tests pin it."""
+    from .loudness import normalize_loudness
+    wavs = vocoder(mels, lens=mel_lens).squeeze(1)
+    hop = wavs.shape[1] // mels.shape[2]
+    lens = mel_lens.tolist() if torch.is_tensor(mel_lens) else [int(v) for v in mel_lens]
+    wav_lens = [hop * max(0, min(int(n), mels.shape[2])) for n in lens]
+    wavs = normalize_loudness(wavs, wav_lens, sampling_rate, target=float(loudness), peak_limit=True)[0]
+    # the peak guard allows a sample of exactly 1.0, which scales to +32768: saturate it (a plain cast would wrap to -32768)
+    wavs = np.clip(wavs.cpu().numpy() * max_wav_value, -32768.0, 32767.0).astype("int16")
+    return [wavs[i][:n] for i, n in enumerate(wav_lens)]

@@ -909,6 +909,47 @@ int ctts_resample(const float* wav, const int32_t* lens, const float* bank, floa
 int ctts_peak_normalize(const float* wav, const int32_t* lens, float* out, int16_t* out_i16, float* peak, int32_t* valid, int B, int N,
                         float max_wav_value, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Loudness on the device (csrc/loudness.hip): ITU-R BS.1770 gated loudness of mono utterances and the gain that
+ * brings them to a target, what the reference does on the host with pyloudnorm (audio/stft.py:226-231).  PARITY with pyloudnorm is
+ * UNPINNED (it is not installed where this project is built); the kernels are pinned against the float64 restatement in
+ * tests/loudness_restate.py.  fp32 samples, lengths int32 device arrays clamped to [0, N]; every recursion state, product and sum is
+ * double.  Stream-ordered, caller-allocated, no host sync, no float atomics, no workgroup waits on another: bit-reproducible, and a row's
+ * result does not depend on B, on N, on the other rows or on the launch geometry.  Samples at and beyond lens[b] are never read.
+ *
+ * TABLES (made on the host, ctts_amd.loudness): a measurement is described by the sorted sample positions at which a block starts or
+ * ends ("edges", edges[0] = 0, edges[n_edges - 1] = INT32_MAX), which cut the time axis into hop segments k = [edges[k], edges[k+1]);
+ * chunk_seg[c], the segment that holds sample c * ctts_loudness_chunk(), for every chunk of every 64-chunk tile that starts below N; and
+ * blocks[j] = {k0, k1}: block j is the union of segments k0 .. k1 - 1.  A tile may touch at most ctts_loudness_tile_slots() segments.
+ * coef (double, ctts_loudness_coef_doubles() words): [0..4] b0 b1 b2 a1 a2 of the first section (a0 = 1), [5..9] of the second,
+ * [16 + 16 (16 l + m - 1) ..] the row-major 4 x 4 matrix A^(chunk 16^l m), l = 0 .. 4, m = 1 .. 16, where A advances the state
+ * (z1, z2 of section one, z1, z2 of section two; transposed direct form II) by one sample of zero input.
+ *
+ * ctts_kweight_energy: wav [B][N] -> hop_sums [B][ceil(N / (64 chunk))][slots] (double; sum of y^2 per tile and segment, y the K-weighted
+ * signal; only tiles that start below lens[b] are written) and peak [B] = max |wav| over the utterance.  workspace:
+ * ctts_loudness_workspace_bytes(B, N) bytes, 8-byte aligned.  Three launches: zero-state chunk responses, a per-utterance scan of the
+ * chunk states with the powers in coef, the energy pass from the true states.  DOMAIN: B <= 65535, 1 <= N <= 2^24.
+ *
+ * ctts_loudness_gate: z_j = (sum of block j's segments) / block_samples for j < n_blocks[b]; l_j = -0.691 + 10 log10 z_j;
+ * Gamma_r = -0.691 + 10 log10 mean{z_j : l_j >= -70} - 10; loudness[b] = -0.691 + 10 log10 mean{z_j : l_j > Gamma_r and l_j > -70}.
+ * No such block: loudness = -inf, valid = 0, gain = 1.  Otherwise gain = 10^((target - loudness) / 20) rounded once to fp32, or, with
+ * peak_limit and peak * gain > 1, the correctly rounded 1 / peak (x g / max |x g|).  curve [B][J] (NULL: not wanted) receives l_j, -inf
+ * at and beyond n_blocks[b].  DOMAIN: J and n_edges - 2 at most ctts_loudness_max_segments().
+ *
+ * ctts_apply_gain: out[b][i] = wav[b][i] * gain[b] (one fp32 rounding) for i < lens[b], 0 beyond; every element written; out may be
+ * wav.  16-byte accesses when N is a multiple of 4 and both pointers are 16-byte aligned. */
+int ctts_loudness_chunk(void);
+int ctts_loudness_tile_slots(void);
+int ctts_loudness_coef_doubles(void);
+int ctts_loudness_max_segments(void);
+size_t ctts_loudness_workspace_bytes(int B, int N);
+int ctts_kweight_energy(const float* wav, const int32_t* lens, const double* coef, const int32_t* edges, const int32_t* chunk_seg,
+                        double* hop_sums, float* peak, int B, int N, int n_edges, int n_chunk_seg, void* workspace, void* stream);
+int ctts_loudness_gate(const double* hop_sums, const int32_t* lens, const int32_t* n_blocks, const int32_t* edges, const int32_t* chunk_seg,
+                       const int32_t* blocks, const float* peak, double* loudness, float* gain, int32_t* valid, double* curve, int B, int N,
+                       int n_edges, int n_chunk_seg, int J, double block_samples, double target, int peak_limit, void* stream);
+int ctts_apply_gain(const float* wav, const int32_t* lens, const float* gain, float* out, int B, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
