@@ -14,5 +14,6 @@ from .vocoder import Generator as HiFiGANGenerator  # noqa: F401
 from .pitch_features import track_pitch, f0_targets, pitch_targets_from_wav  # noqa: F401
 from .preprocess import trim_silence, attention_prior, outlier_stats, merge_moments, DatasetStats, process_batch, process_batch_loudness  # noqa: F401
 from .metrics import mel_cepstrum, dtw, path_metrics, compare_mels, compare_wavs  # noqa: F401
+from .metrics import stoi, si_sdr, mr_stft_distance, waveform_metrics, summarize_waveform  # noqa: F401
 from .resample import resample_filter, peak_normalize  # noqa: F401  (the resampler itself is resample.resample: `resample` names the module)
 from .loudness import kweighting, integrated_loudness, loudness_curve, normalize_loudness  # noqa: F401

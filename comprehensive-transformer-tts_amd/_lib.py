@@ -225,6 +225,10 @@ _SIGNATURES = {
     "ctts_loudness_gate": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                            C.c_double, C.c_int, _vp],
     "ctts_apply_gain": [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp],
+    "ctts_stoi_max_frames": [],
+    "ctts_stoi": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp],
+    "ctts_si_sdr": [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp],
+    "ctts_mr_stft": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
     "ctts_comm_unique_id": [_vp],
     "ctts_comm_create": [C.POINTER(_vp), _i32, _i32, _vp],
     "ctts_comm_destroy": [_vp],
@@ -236,7 +240,8 @@ EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["ctts_last_error", "ctts_version"
                                                "ctts_workspace_error_word", "ctts_fastformer_workspace_floats",
                                                "ctts_griffinlim_workspace_bytes", "ctts_griffinlim_state_floats",
                                                "ctts_pitch_track_workspace_bytes", "ctts_trim_silence_workspace_bytes",
-                                               "ctts_dtw_workspace_bytes", "ctts_loudness_workspace_bytes"])
+                                               "ctts_dtw_workspace_bytes", "ctts_loudness_workspace_bytes", "ctts_stoi_workspace_bytes",
+                                               "ctts_si_sdr_workspace_bytes", "ctts_mr_stft_workspace_bytes"])
 ADAM_STATE_FLOATS = 3 + 2048          # CTTS_ADAM_STATE_FLOATS of include/ctts.h
 ABI_VERSION = 2                       # ctts_version() of the library this binding was written for
 
@@ -293,6 +298,12 @@ def load():
     lib.ctts_dtw_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ctts_loudness_workspace_bytes.restype = C.c_size_t
     lib.ctts_loudness_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.ctts_stoi_workspace_bytes.restype = C.c_size_t
+    lib.ctts_stoi_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.ctts_si_sdr_workspace_bytes.restype = C.c_size_t
+    lib.ctts_si_sdr_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.ctts_mr_stft_workspace_bytes.restype = C.c_size_t
+    lib.ctts_mr_stft_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ctts_relmha_workspace_floats.restype = C.c_size_t
     lib.ctts_relmha_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int]
     _lib = lib

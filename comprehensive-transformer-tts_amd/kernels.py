@@ -2066,3 +2066,86 @@ def apply_gain(wav, lens, gain, out=None):
             raise _lib.CttsError(f"apply_gain: out {tuple(out.shape)} does not match wav {tuple(wav.shape)}")
     _lib.check(_lib.load().ctts_apply_gain(_p(wav), _p(lens), _p(gain), _p(out), B, N, _stream()), "ctts_apply_gain")
     return out
+
+
+# ---- waveform metrics: STOI / ESTOI, SI-SDR, multi-resolution STFT distance (csrc/wavmetrics.hip) -----------------------------------
+STOI_FRAME, STOI_HOP = 256, 128
+MR_STFT_SIZES = (512, 1024, 2048)
+WAVMETRICS_MAX_SAMPLES = 1 << 30      # per row (SI-SDR, MR-STFT)
+
+
+def stoi_max_frames():
+    """frames of 256 samples at hop 128 one utterance may hold in `stoi`"""
+    return int(_lib.load().ctts_stoi_max_frames())
+
+
+def _wav_pair(ref, syn, lens, what):
+    for t, name in ((ref, "ref"), (syn, "syn")):
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise _lib.CttsError(f"{what}: expected {name} [B, N]")
+        _p(t)
+        _al4(_f32c(t, name), name)
+    if ref.shape != syn.shape:
+        raise _lib.CttsError(f"{what}: ref {tuple(ref.shape)} and syn {tuple(syn.shape)} must have one shape")
+    B, N = ref.shape
+    if B < 1 or N < 1:
+        raise _lib.CttsError(f"{what}: empty batch {tuple(ref.shape)}")
+    if B > 65535 or N > WAVMETRICS_MAX_SAMPLES:
+        raise _lib.CttsError(f"{what}: at most 65535 utterances of 2^30 samples per call, got {B} x {N}")
+    _lens_i32(lens, B, what)
+    return B, N
+
+
+def _window_f64(window, n, what):
+    _p(window)
+    if window.dtype != torch.float64 or window.dim() != 1 or window.numel() != n or not window.is_contiguous():
+        raise _lib.CttsError(f"{what}: window must be {n} contiguous float64 words on the device")
+
+
+def stoi(ref, syn, lens, window):
+    """ref, syn [B,N] float32 at 10 kHz, lens int32 [B], window float64 [256] -> (stoi float64 [B], estoi float64 [B],
+    counts int32 [B,3] = frames, kept frames, segments)"""
+    B, N = _wav_pair(ref, syn, lens, "stoi")
+    _window_f64(window, STOI_FRAME, "stoi")
+    frames = (N - STOI_FRAME) // STOI_HOP + 1 if N >= STOI_FRAME else 0
+    if frames > stoi_max_frames():
+        raise _lib.CttsError(f"stoi: rows of {N} samples hold {frames} frames; at most {stoi_max_frames()} per utterance")
+    lib = _lib.load()
+    dev = ref.device
+    ws = torch.empty(max(lib.ctts_stoi_workspace_bytes(B, N) // 8, 1), dtype=torch.float64, device=dev)
+    d = torch.empty(B, dtype=torch.float64, device=dev)
+    e = torch.empty(B, dtype=torch.float64, device=dev)
+    counts = torch.empty(B, 3, dtype=torch.int32, device=dev)
+    _lib.check(lib.ctts_stoi(_p(ref), _p(syn), _p(lens), _p(window), _p(d), _p(e), _p(counts), B, N, _p(ws), _stream()), "ctts_stoi")
+    return d, e, counts
+
+
+def si_sdr(ref, syn, lens):
+    """ref, syn [B,N] float32, lens int32 [B] -> float64 [B] in dB"""
+    B, N = _wav_pair(ref, syn, lens, "si_sdr")
+    lib = _lib.load()
+    ws = torch.empty(max(lib.ctts_si_sdr_workspace_bytes(B, N) // 8, 1), dtype=torch.float64, device=ref.device)
+    out = torch.empty(B, dtype=torch.float64, device=ref.device)
+    _lib.check(lib.ctts_si_sdr(_p(ref), _p(syn), _p(lens), _p(out), B, N, _p(ws), _stream()), "ctts_si_sdr")
+    return out
+
+
+def mr_stft(ref, syn, lens, window, n_fft, hop):
+    """one resolution: ref, syn [B,N] float32, lens int32 [B], window float64 [win] -> (float64 [B,3] = spectral convergence, log-magnitude
+    distance, log-spectral distance in dB; frames int32 [B])"""
+    B, N = _wav_pair(ref, syn, lens, "mr_stft")
+    n_fft, hop = int(n_fft), int(hop)
+    if n_fft not in MR_STFT_SIZES:
+        raise _lib.CttsError(f"mr_stft: n_fft must be one of {MR_STFT_SIZES}, got {n_fft}")
+    if not torch.is_tensor(window) or window.dim() != 1 or not 1 <= window.numel() <= n_fft or hop < 1:
+        raise _lib.CttsError(f"mr_stft: need a window of 1 .. n_fft = {n_fft} samples and hop >= 1, got hop {hop}")
+    win = window.numel()
+    _window_f64(window, win, "mr_stft")
+    lib = _lib.load()
+    dev = ref.device
+    ws = torch.empty(max(lib.ctts_mr_stft_workspace_bytes(B, N, hop, win) // 8, 1), dtype=torch.float64, device=dev)
+    out = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    frames = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.ctts_mr_stft(_p(ref), _p(syn), _p(lens), _p(window), _p(out), _p(frames), B, N, n_fft, hop, win, _p(ws), _stream()),
+               "ctts_mr_stft")
+    return out, frames

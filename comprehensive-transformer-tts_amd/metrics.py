@@ -21,9 +21,49 @@ sqrt(sum over pairs voiced in both of (1200 log2(f0_ref / f0_syn))^2 / n_voiced)
 A quantity with a zero denominator is NaN, and its count (path_len, n_voiced) says why.
 
 All calls are stream-ordered; lengths are device tensors, nothing synchronises, nothing runs on the CPU: CPU tensors raise.
+
+WAVEFORM METRICS (csrc/wavmetrics.hip): the figures the vocoder literature reports for copy-synthesis, where the synthesised waveform is
+sample-aligned with its recording and no DTW is needed.
+
+  stoi                STOI or ESTOI (intelligibility) per utterance, with the frame counts
+  si_sdr              scale-invariant signal-to-distortion ratio in dB
+  mr_stft_distance    the Parallel-WaveGAN multi-resolution STFT distances: spectral convergence, log-magnitude, log-spectral distance
+  waveform_metrics    the three chained; the resample to STOI's 10 kHz happens once
+  summarize_waveform  corpus means over the utterances that have a value (the one function here that copies to the host)
+
+All signals are [B, N] float32 device tensors, `lens` host sequences (checked) or device tensors (clamped); samples at and beyond
+lens[b] are never read.  The float64 restatement in tests/wavmetrics_restate.py is the contract:
+
+STOI / ESTOI (Taal et al. 2011; Jensen & Taal 2016).  fs = 10000, frames of 256 at hop 128, FFT 512 (frame zero-padded on the right),
+window w = np.hanning(258)[1:-1], J = 15 third-octave bands, N = 30 frames per segment, beta = -15 dB, dynamic range 40 dB, eps = 2^-52.
+ 1. Utterance frame i starts at 128 i, i < F = (len - 256) // 128 + 1 (F = 0 below 256 samples).
+ 2. Silent-frame removal: e_i = 20 log10(||w x_i||_2 + eps) on the REFERENCE only; frame i is kept iff e_i > max_i e_i - 40.  The kept
+    frames of both signals, windowed, are overlap-added at hop 128 in kept order into x', y' (K kept frames: 128 (K - 1) + 256 samples).
+ 3. Frames of x', y' (same framing, same window again) go to 512-point spectra; band amplitude = sqrt(sum_{k in band j} |X_k|^2), band j
+    = bins [lo_j, hi_j) with lo, hi the bins nearest to 150 2^((2j - 1) / 6) and 150 2^((2j + 1) / 6) Hz on the grid k 10000 / 512:
+    (7,9) (9,11) (11,14) (14,17) (17,22) (22,27) (27,34) (34,43) (43,55) (55,69) (69,87) (87,109) (109,138) (138,174) (174,219).
+ 4. For every m = 30 .. M (M = K frames of x') and the 15 x 30 blocks X_m, Y_m of band amplitudes over frames m - 30 .. m - 1:
+    STOI: per band row alpha = ||x|| / (||y|| + eps), y' = min(alpha y, x (1 + 10^(15/20))); d_jm = the correlation of the mean-removed
+    rows, each normalised by (norm + eps); the result is the mean over j, m.  ESTOI: rows mean-removed and normalised, then columns
+    mean-removed and normalised (each by norm + eps); d_m = sum(Xn * Yn) / 30; the result is the mean over m.
+ 5. M < 30, or a reference whose largest frame energy is 0: NaN and segments = 0 (kept is then what rule 2 gives: every frame).
+ 6. Counts per utterance: frames (F), kept (K), segments (M - 29).
+ 7. rate != 10000: both signals first go through `resample.resample(..., rate, 10000, "kaiser_best")`, one ragged batch each.
+PARITY with pystoi is UNPINNED: it is not installed where this project is built and tested, and its resampling filter differs from this
+project's.  With rate = 10000 the definition above is pystoi's, step by step.
+
+SI-SDR.  With the means over [0, len) removed: t = (<y,x> / <x,x>) x, si_sdr = 10 log10(||t||^2 / ||y - t||^2) dB; NaN for len = 0 or
+<x,x> = 0, +inf where y = g x exactly (the device finds the residual exactly 0 for g a power of two).
+
+MULTI-RESOLUTION STFT DISTANCE.  Resolutions (n_fft, hop, win), default (512, 50, 240), (1024, 120, 600), (2048, 240, 1200); window =
+periodic Hann 0.5 - 0.5 cos(2 pi n / win), zero-padded on the right to n_fft; frames start at i hop for i < (len - win) // hop + 1, no
+padding; |X| = sqrt(max(re^2 + im^2, 1e-7)).  Per utterance and resolution sc = || |X| - |Y| ||_F / || |X| ||_F, log_mag =
+mean | ln|X| - ln|Y| |, lsd_db = mean over frames of sqrt(mean over bins of (20 log10|X| - 20 log10|Y|)^2); no frame: NaN.
+n_fft in {512, 1024, 2048} and win <= n_fft; anything else raises.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import kernels as K
@@ -166,3 +206,120 @@ def summarize(result):
         return torch.where(n > 0, v.double() * n, zero).sum() / total
     return {"mcd_db": weighted(result["mcd_db"]), "lf0_rmse_cents": torch.sqrt(result["sq_cents"].double().sum() / voiced),
             "vuv_error": weighted(result["vuv_error"]), "path_len": total, "n_voiced": voiced}
+
+
+# ---- waveform metrics (module docstring, WAVEFORM METRICS) ------------------------------------------------------------------------
+STOI_RATE = 10000
+MR_STFT_DEFAULT = ((512, 50, 240), (1024, 120, 600), (2048, 240, 1200))
+_windows = {}
+
+
+def stoi_window():
+    """the 256-point analysis window of STOI, float64 on the host"""
+    return np.hanning(K.STOI_FRAME + 2)[1:-1].copy()
+
+
+def mr_stft_window(win):
+    """periodic Hann of `win` samples, float64 on the host"""
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(int(win)) / float(int(win)))
+
+
+def _window(kind, n, dev):
+    key = (kind, n, str(dev))
+    if key not in _windows:
+        _windows[key] = torch.from_numpy(stoi_window() if kind == "stoi" else mr_stft_window(n)).to(dev)
+    return _windows[key]
+
+
+def _pair(ref, syn, lens, what):
+    ref, syn = _dev(ref, what, "ref"), _dev(syn, what, "syn")
+    if ref.dim() != 2 or ref.shape != syn.shape or ref.shape[0] < 1 or ref.shape[1] < 1:
+        raise CttsError(f"{what}: expected two non-empty [B, N] waveforms of one shape, got {tuple(ref.shape)} / {tuple(syn.shape)}")
+    return _f32(ref), _f32(syn), _lens(lens, ref.shape[0], ref.shape[1], f"{what} lens", ref.device)
+
+
+def _to_stoi_rate(ref, syn, lens, rate):
+    rate = int(rate)
+    if rate == STOI_RATE:
+        return ref, syn, lens
+    from . import resample as RS
+    try:
+        r, out_lens = RS.resample(ref, lens, rate, STOI_RATE, "kaiser_best")
+        s, _ = RS.resample(syn, lens, rate, STOI_RATE, "kaiser_best")
+    except ValueError as e:
+        raise CttsError(str(e)) from None
+    return r, s, out_lens
+
+
+def _stoi_both(ref, syn, lens, rate):
+    ref, syn, lens = _to_stoi_rate(ref, syn, lens, rate)
+    limit = K.STOI_HOP * (K.stoi_max_frames() - 1) + K.STOI_FRAME + K.STOI_HOP - 1
+    if ref.shape[1] > limit:
+        raise CttsError(f"stoi: rows of {ref.shape[1]} samples at {STOI_RATE} Hz exceed the {K.stoi_max_frames()} frames ({limit} samples, "
+                        f"{limit / STOI_RATE:.1f} s) one utterance may hold - cut the utterances")
+    d, e, counts = K.stoi(ref, syn, lens, _window("stoi", K.STOI_FRAME, ref.device))
+    return d, e, counts
+
+
+def stoi(ref, syn, lens, rate, extended=False):
+    """ref, syn [B,N] at `rate` Hz, lens [B] or None -> dict of device tensors: stoi float64 [B] (ESTOI with extended=True; NaN without
+    a segment), frames, kept, segments int32 [B]."""
+    ref, syn, lens = _pair(ref, syn, lens, "stoi")
+    d, e, counts = _stoi_both(ref, syn, lens, rate)
+    return {"stoi": e if extended else d, "frames": counts[:, 0], "kept": counts[:, 1], "segments": counts[:, 2]}
+
+
+def si_sdr(ref, syn, lens):
+    """ref, syn [B,N], lens [B] or None -> float64 [B] in dB on the device"""
+    ref, syn, lens = _pair(ref, syn, lens, "si_sdr")
+    return K.si_sdr(ref, syn, lens)
+
+
+def _resolutions(resolutions):
+    try:
+        res = [tuple(int(v) for v in r) for r in resolutions]
+    except (TypeError, ValueError):
+        raise CttsError(f"mr_stft_distance: resolutions must be (n_fft, hop, win) triples, got {resolutions!r}") from None
+    if not res or any(len(r) != 3 for r in res):
+        raise CttsError(f"mr_stft_distance: resolutions must be (n_fft, hop, win) triples, got {resolutions!r}")
+    for n_fft, hop, win in res:
+        if n_fft not in K.MR_STFT_SIZES or not 1 <= win <= n_fft or hop < 1:
+            raise CttsError(f"mr_stft_distance: resolution ({n_fft}, {hop}, {win}): n_fft must be one of {K.MR_STFT_SIZES}, "
+                            "1 <= win <= n_fft and hop >= 1")
+    return res
+
+
+def mr_stft_distance(ref, syn, lens, resolutions=MR_STFT_DEFAULT):
+    """ref, syn [B,N], lens [B] or None -> dict of [B, R] device tensors: sc, log_mag, lsd_db (float64; NaN without a frame), frames int32"""
+    res = _resolutions(resolutions)
+    ref, syn, lens = _pair(ref, syn, lens, "mr_stft_distance")
+    outs, frames = zip(*(K.mr_stft(ref, syn, lens, _window("hann", win, ref.device), n_fft, hop) for n_fft, hop, win in res))
+    v = torch.stack(outs, dim=1)
+    return {"sc": v[:, :, 0], "log_mag": v[:, :, 1], "lsd_db": v[:, :, 2], "frames": torch.stack(frames, dim=1)}
+
+
+def waveform_metrics(ref, syn, lens, rate):
+    """The three chained: stoi, estoi, frames, kept, segments [B]; si_sdr [B]; sc, log_mag, lsd_db, mr_frames [B, R] at the default
+    resolutions.  SI-SDR and the STFT distances are taken at `rate`, STOI and ESTOI on one resample to 10 kHz."""
+    ref, syn, lens = _pair(ref, syn, lens, "waveform_metrics")
+    d, e, counts = _stoi_both(ref, syn, lens, rate)
+    mr = mr_stft_distance(ref, syn, lens)
+    return {"stoi": d, "estoi": e, "frames": counts[:, 0], "kept": counts[:, 1], "segments": counts[:, 2], "si_sdr": K.si_sdr(ref, syn, lens),
+            "sc": mr["sc"], "log_mag": mr["log_mag"], "lsd_db": mr["lsd_db"], "mr_frames": mr["frames"]}
+
+
+def summarize_waveform(result):
+    """Corpus numbers of a `waveform_metrics` / `stoi` / `mr_stft_distance` result, or of {"si_sdr": si_sdr(...)}: for every float
+    entry {"mean": the mean over the utterances whose value is not NaN (per resolution for [B, R] entries; NaN when there is none),
+    "count": how many those are}.  Host floats and ints: this is the one function of the module that copies to the host."""
+    out = {}
+    for name, v in result.items():
+        if not torch.is_tensor(v) or not v.is_floating_point():
+            continue
+        a = v.detach().double().cpu().numpy()
+        ok = ~np.isnan(a)
+        n = ok.sum(axis=0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = np.where(ok, a, 0.0).sum(axis=0) / n
+        out[name] = {"mean": mean.tolist(), "count": n.tolist()}
+    return out

@@ -950,6 +950,42 @@ int ctts_loudness_gate(const double* hop_sums, const int32_t* lens, const int32_
                        int n_edges, int n_chunk_seg, int J, double block_samples, double target, int peak_limit, void* stream);
 int ctts_apply_gain(const float* wav, const int32_t* lens, const float* gain, float* out, int B, int N, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Waveform metrics on the device (csrc/wavmetrics.hip): STOI / ESTOI, SI-SDR and the multi-resolution STFT
+ * distances of a synthesised utterance `syn` against its sample-aligned recording `ref`, both [B][N] fp32 with one length per pair
+ * (int32 device array, clamped to [0, N]).  The definitions are those of the ctts_amd.metrics docstring, pinned by the float64
+ * restatement in tests/wavmetrics_restate.py; PARITY with pystoi is UNPINNED (it is not installed where this project is built, and it
+ * resamples with another filter).  The samples enter exactly; every product, transform and sum is double.  Stream-ordered,
+ * caller-allocated, no host sync, no float atomics, no workgroup waits on another: bit-reproducible, and a row's result does not depend
+ * on B, on N, on the other rows or on the launch geometry.  Samples at and beyond lens[b] are never read.  Every output element is
+ * written.  Workspaces are 8-byte aligned and need no initialisation.
+ *
+ * ctts_stoi: the signals are at 10 kHz.  window: the 256 doubles of the analysis window.  Frames of 256 at hop 128; the frames of ref
+ * whose energy 20 log10(||w x_i|| + 2^-52) exceeds the largest one - 40 dB are kept, both signals' kept frames are windowed and
+ * overlap-added (never materialised: the spectrum kernel gathers through the kept-index list), framed and windowed again, transformed
+ * with 512 points and summed into 15 third-octave band amplitudes; every run of 30 such frames gives one STOI and one ESTOI value.
+ * stoi [B], estoi [B]: their means, NaN without a segment or when ref's largest frame energy is 0.  counts [B][3]: frames, kept frames,
+ * segments.  DOMAIN: B <= 65535; rows of N samples may hold at most ctts_stoi_max_frames frames (8192: 81.9 s, N <= 1048831); a
+ * longer row is refused before any launch, and the workspace query returns 0 for it.
+ *
+ * ctts_si_sdr: out [B] = 10 log10(||t||^2 / ||y - t||^2) in dB with the means over [0, len) removed and t = (<y,x> / <x,x>) x, from
+ * the five sums of x, y, xy, xx, yy (tiles of 4096 samples, then the tiles in index order).  NaN for len = 0 or <x,x> = 0, +inf where
+ * the residual vanishes (y = 2^k x does so exactly).  DOMAIN: B <= 65535, N <= 2^30.
+ *
+ * ctts_mr_stft: one resolution of the Parallel-WaveGAN distances.  window: win doubles, zero-padded on the right to n_fft; frames start
+ * at i hop for i < (len - win) / hop + 1, no padding; |X| = sqrt(max(re^2 + im^2, 1e-7)).  out [B][3]: spectral convergence
+ * || |X| - |Y| ||_F / || |X| ||_F, mean | ln|X| - ln|Y| |, mean over frames of the root mean over bins of (20 log10|X| - 20 log10|Y|)^2;
+ * NaN without a frame.  frames [B].  DOMAIN: n_fft 512, 1024 or 2048; 1 <= win <= n_fft; hop >= 1; B <= 65535; N <= 2^30. */
+int ctts_stoi_max_frames(void);
+size_t ctts_stoi_workspace_bytes(int B, int N);
+int ctts_stoi(const float* ref, const float* syn, const int32_t* lens, const double* window, double* stoi, double* estoi, int32_t* counts,
+              int B, int N, void* workspace, void* stream);
+size_t ctts_si_sdr_workspace_bytes(int B, int N);
+int ctts_si_sdr(const float* ref, const float* syn, const int32_t* lens, double* out, int B, int N, void* workspace, void* stream);
+size_t ctts_mr_stft_workspace_bytes(int B, int N, int hop, int win);
+int ctts_mr_stft(const float* ref, const float* syn, const int32_t* lens, const double* window, double* out, int32_t* frames, int B, int N,
+                 int n_fft, int hop, int win, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

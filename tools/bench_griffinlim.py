@@ -24,8 +24,10 @@ a default angles=None call (host draw + copy) against a seed= call (phase drawn 
 
 --quality (opt-in, both reports) adds the mel-cepstral distortion (ctts_amd.metrics, MFCC-style: the DCT of this project's log-mel, not
 WORLD / SPTK mel-cepstra) of each Griffin-Lim output, its log-mel re-extracted by `TacotronSTFT`, against the log-mel of the magnitudes
-it was given, frame by frame (align="none"); with --momentum also of the fast output against the plain one (`compare_wavs`).  Without
-the flag the output is unchanged."""
+it was given, frame by frame (align="none"); with --momentum also of the fast output against the plain one (`compare_wavs`), and the
+sample-aligned waveform metrics of the fast output against the plain one (`waveform_metrics`: STOI, ESTOI, SI-SDR, multi-resolution
+STFT distances; corpus means - two phase reconstructions of one magnitude, so SI-SDR is low by construction; the magnitudes are
+synthetic, there is no recording to take them against).  Without the flag the output is unchanged."""
 import argparse
 import json
 import os
@@ -187,7 +189,9 @@ def fast_report(a):
         tac = audio.TacotronSTFT(NFFT, HOP, NFFT, 80, SR, 0, 8000).to(dev)
         sl = torch.tensor(samples, dtype=torch.int32, device=dev)
         r = M.summarize(M.compare_wavs(plain_out, sl, fast_out, sl, tac, align="none"))
+        wm = M.summarize_waveform(M.waveform_metrics(plain_out, fast_out, sl, SR))
         res["quality"] = {"plain_mcd_db_vs_input_mel": mcd_vs_input(mag, lens, plain_out),
+                          "momentum_vs_plain_waveform": {k: wm[k]["mean"] for k in ("stoi", "estoi", "si_sdr", "sc", "log_mag", "lsd_db")},
                           "momentum_mcd_db_vs_input_mel": mcd_vs_input(mag, lens, fast_out),
                           "momentum_vs_plain": {"mcd_db": round(r["mcd_db"].item(), 5), "lf0_rmse_cents": r["lf0_rmse_cents"].item(),
                                                 "vuv_error": r["vuv_error"].item(), "n_voiced": int(r["n_voiced"].item())}}

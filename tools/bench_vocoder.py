@@ -27,7 +27,9 @@ against the native fp32 output.
 (ctts_amd.metrics, MFCC-style: the DCT of this project's log-mel, not WORLD / SPTK mel-cepstra) of each native output, its log-mel
 re-extracted by `TacotronSTFT`, against the input mel's own cepstra frame by frame (align="none"), and with --precision fp16 of the fp16
 output against the fp32 output (`compare_wavs`).  The weights here are random, so the first figure says what the network does to a
-mel, not how a trained vocoder sounds; the second is the distance between the two modes.  Without the flag the output is unchanged."""
+mel, not how a trained vocoder sounds; the second is the distance between the two modes, and comes with the sample-aligned waveform
+metrics of the fp16 output against the fp32 output (`waveform_metrics`: STOI, ESTOI, SI-SDR, multi-resolution STFT distances; corpus
+means).  The mels here are synthetic, so there is no recording to take those against.  Without the flag the output is unchanged."""
 import argparse
 import json
 import os
@@ -82,6 +84,9 @@ def quality(view, wavs):
         r = M.summarize(M.compare_wavs(wavs[names[0]][:, 0], None, wavs[names[1]][:, 0], None, stft, align="none"))
         out[f"{names[1]}_vs_{names[0]}"] = {"mcd_db": round(r["mcd_db"].item(), 5), "lf0_rmse_cents": r["lf0_rmse_cents"].item(),
                                            "vuv_error": r["vuv_error"].item(), "n_voiced": int(r["n_voiced"].item())}
+        # the sample-aligned waveform metrics between the two modes (the mels here are synthetic: there is no recording to compare with)
+        wm = M.summarize_waveform(M.waveform_metrics(wavs[names[0]][:, 0], wavs[names[1]][:, 0], None, SR))
+        out[f"{names[1]}_vs_{names[0]}"]["waveform"] = {k: wm[k]["mean"] for k in ("stoi", "estoi", "si_sdr", "sc", "log_mag", "lsd_db")}
     return out
 
 
