@@ -135,6 +135,7 @@ _SIGNATURES = {
     "ctts_weighted_colsum": [_vp, _vp, _vp, _i64, C.c_int, _f32, C.c_int, _vp, _vp, _vp],
     "ctts_epilogue_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, C.c_int, C.c_int, _f32, _vp, _u32, _f32, C.c_int, _vp, _vp, _vp],
     "ctts_row_tile_map": [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp],
+    "ctts_batch_tile_map": [_vp] + [C.c_int] * 9 + [_vp, C.c_size_t, _vp],
     "ctts_conv_weight_repack": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "ctts_lr_index": [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
     "ctts_lr_gather_fwd": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
@@ -241,7 +242,8 @@ EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["ctts_last_error", "ctts_version"
                                                "ctts_griffinlim_workspace_bytes", "ctts_griffinlim_state_floats",
                                                "ctts_pitch_track_workspace_bytes", "ctts_trim_silence_workspace_bytes",
                                                "ctts_dtw_workspace_bytes", "ctts_loudness_workspace_bytes", "ctts_stoi_workspace_bytes",
-                                               "ctts_si_sdr_workspace_bytes", "ctts_mr_stft_workspace_bytes"])
+                                               "ctts_si_sdr_workspace_bytes", "ctts_mr_stft_workspace_bytes",
+                                               "ctts_batch_tile_map_ints"])
 ADAM_STATE_FLOATS = 3 + 2048          # CTTS_ADAM_STATE_FLOATS of include/ctts.h
 ABI_VERSION = 2                       # ctts_version() of the library this binding was written for
 
@@ -304,6 +306,8 @@ def load():
     lib.ctts_si_sdr_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.ctts_mr_stft_workspace_bytes.restype = C.c_size_t
     lib.ctts_mr_stft_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.ctts_batch_tile_map_ints.restype = C.c_size_t
+    lib.ctts_batch_tile_map_ints.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ctts_relmha_workspace_floats.restype = C.c_size_t
     lib.ctts_relmha_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int]
     _lib = lib

@@ -13,6 +13,7 @@
 // Host side: tile_plan / gemm_route decide which kernel takes a descriptor, ctts_gemm launches it.
 #include "ctts_common.h"
 #include "gemm_common.h"
+#include "batch_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -48,6 +49,12 @@ __device__ __forceinline__ void batch_limits(const ctts_gemm_desc& d, int z0, bo
     if (d.lim_n) Nv = min(Nv, L);
     if (d.lim_k) Kv = min(Kv, L);
   }
+}
+
+// What the tile order of a length-limited batched launch depends on (batch_plan.h); "write everything" as zero_outside_limits has it.
+__host__ __device__ __forceinline__ BatchPlanGeom batch_plan_geom(const ctts_gemm_desc& d, int BM, int BN, int nbins) {
+  return BatchPlanGeom{d.M, d.N, d.K, BM, BN, BK, d.nb0 * d.nb1, d.nb1, d.lim_m != 0, d.lim_n != 0, d.lim_k != 0,
+                       d.split_overwrite != 0 && d.split_k <= 1, nbins};
 }
 
 // The K range of this workgroup: everything, or the share of its split (k_granule = `granule`).  false: an empty share, nothing to write.
@@ -437,8 +444,13 @@ struct FetchTraits {
   // tile orders besides the XCD-contiguous one - device-built tile_map schedule, tile_group_n, the natural-order sentinel: only
   // tile_plan's buffer routes are set up with them; pointer fetch always uses the XCD remap
   static constexpr bool kTileOrders = kBuffer;
-  // always plain blockIdx order: the valid tiles of a short utterance are its FIRST rows / columns, and the XCD-contiguous remap would
-  // put all of them on the first XCDs
+  // never the XCD-contiguous remap: the valid tiles of a short utterance are its FIRST rows / columns, and the remap would put all of
+  // them on the first XCDs.  Plain blockIdx order (x = tile, z = batch) has the same fault one level down: consecutive workgroups are
+  // dealt over the CUs, so with 32 m-tiles x 32 batches one CU holds tile j of batches z, z + 8, z + 16, z + 24 - the CUs with low j
+  // carry four long K loops, those with high j one or none, and the launch lasts as long as its most loaded CU (O = P V with all
+  // lengths 512 on T = 1024 operands: 40.5 us, the same work on T = 512 operands: 25.7 us).  With a plan in d.tile_map
+  // (ctts_batch_tile_map, batch_plan.h) the workgroup's linear id picks (batch, tile) from a permutation that deals the active tiles,
+  // heaviest first, evenly over the CUs; what a tile computes does not depend on where it runs.  Without one: plain order.
   static constexpr bool kNaturalOrder = F == Fetch::BufferPartial;
   // a tile the schedule lists as active skips the padded-tile test (the schedule was built with the same rule)
   static constexpr bool kTrustSchedule = kTileOrders;
@@ -486,17 +498,28 @@ __global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_tile_kernel(const c
   __shared__ __attribute__((aligned(16))) float smem[A_SZ + B_SZ];
   float* sA = smem;
   float* sB = smem + A_SZ;
-  const int z = blockIdx.z;
+  int z = blockIdx.z;
   const int split = blockIdx.y;                         // K split (grid.y = split_k, 1 when off); z = batch index
-  const int z0 = z / d.nb1, z1 = z - z0 * d.nb1;
   const bool limited = FT::kLensLimits && (FT::kLensGiven || d.lens);      // per-batch valid lengths (attention over non-padded tokens only)
-  int Mv, Nv, Kv;
-  batch_limits(d, z0, limited, Mv, Nv, Kv);
   // ---- which tile
   const int tiles_n = (d.N + BN - 1) / BN;
   int wg, tm;
   bool scheduled_active = false;
-  if (FT::kTileOrders && BM == 64 && A_KC && d.tile_map && !natural_order(d)) {
+  if constexpr (FT::kNaturalOrder) {
+    wg = blockIdx.x;
+    if (d.tile_map && !natural_order(d)) {
+      // length-balanced order: the workgroup's place in the launch names its item in the device-built plan.  A plan made for another
+      // launch geometry is not followed (plain order); ids the plan does not list have nothing to do, not even zeros to write.
+      const int32_t* plan = d.tile_map;
+      const unsigned lin = blockIdx.z * gridDim.x + blockIdx.x;
+      if (plan[2] == (int32_t)(gridDim.x * gridDim.z) && plan[3] == batch_plan_key(batch_plan_geom(d, BM, BN, 1))) {
+        if (lin >= (unsigned)plan[1]) return;
+        batch_plan_unpack(plan[BATCH_PLAN_HDR + lin], z, wg);
+        if (z >= (int)gridDim.z || wg >= (int)gridDim.x) return;      // never an address from a damaged plan
+      }
+    }
+    tm = wg / tiles_n;
+  } else if (FT::kTileOrders && BM == 64 && A_KC && d.tile_map && !natural_order(d)) {
     // device-built schedule: active m-tiles first, natural workgroup order (round-robin over the XCDs)
     wg = blockIdx.x;
     int r = wg / tiles_n;
@@ -508,12 +531,15 @@ __global__ __launch_bounds__(256, CTTS_GEMM_WAVES) void gemm_tile_kernel(const c
     }
     tm = d.tile_map[1 + r];
     scheduled_active = FT::kTrustSchedule && r < d.tile_map[0];
-  } else if (FT::kNaturalOrder || (FT::kTileOrders && natural_order(d))) {
+  } else if (FT::kTileOrders && natural_order(d)) {
     wg = blockIdx.x;
     tm = wg / tiles_n;
   } else {
     xcd_tile_order(gridDim.x, tiles_n, true, wg, tm);
   }
+  const int z0 = z / d.nb1, z1 = z - z0 * d.nb1;
+  int Mv, Nv, Kv;
+  batch_limits(d, z0, limited, Mv, Nv, Kv);
   const int row0 = tm * BM, col0 = (wg % tiles_n) * BN;
   float* Cb = d.C + z0 * d.sC0 + z1 * d.sC1;
   // ---- tiles with nothing to multiply
@@ -1051,6 +1077,24 @@ __global__ __launch_bounds__(64) void row_tile_map_kernel(const int32_t* __restr
   if (lane == 0) map[0] = n_act;
 }
 
+// The plan of batch_plan.h for one launch geometry, from the lengths on the device: thread i places item i.  map: BATCH_PLAN_HDR +
+// n_items int32 (the host checked batch_plan_fits and the size).
+__global__ __launch_bounds__(256) void batch_tile_map_kernel(const BatchPlanGeom g, const int32_t* __restrict__ lens, int32_t* __restrict__ map) {
+  const int n_items = (int)batch_plan_items(g), tiles = n_items / g.nbatch;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n_items; i += gridDim.x * 256) {
+    const int z = i / tiles, tile = i - z * tiles;
+    int n_active;
+    const int slot = batch_plan_slot(g, lens, z, tile, n_active);
+    map[BATCH_PLAN_HDR + slot] = batch_plan_pack(z, tile);
+    if (i == 0) {
+      map[0] = n_active;
+      map[1] = batch_plan_listed(g, n_active);
+      map[2] = n_items;
+      map[3] = batch_plan_key(g);
+    }
+  }
+}
+
 // Second launch of a split-K GEMM: C[m, n] += alpha * (P_0 + P_1 + ... )[m, n] in split order (fixed: bit-reproducible), for the rows /
 // columns / batches the GEMM kernels computed - per-batch length limits, tiles of padded rows (zero-filled by the GEMM, skipped here) and
 // splits whose K range was empty (never written) follow the kernels' own predicates.  One thread per 4 columns, all splits' loads in flight.
@@ -1114,6 +1158,39 @@ extern "C" int ctts_row_tile_map(const int32_t* row_lens, int row_T, int row_hal
   return 0;
 }
 
+// the length-limited batched launches run on 64 x 64 tiles (tile_plan: BUF64 -> Fetch::BufferPartial); bins = the CUs of the device
+static BatchPlanGeom batch_map_geom(int nb0, int nb1, int M, int N, int K, int lim_m, int lim_n, int lim_k, int write_all) {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+              ? prop.multiProcessorCount : 256;
+    cus = ctts_env_int("CTTS_BATCH_BINS", cus);          // tuning knob
+    if (cus < 1) cus = 256;
+  }
+  return BatchPlanGeom{M, N, K, 64, 64, BK, nb0 * nb1, nb1, lim_m != 0, lim_n != 0, lim_k != 0, write_all != 0, cus};
+}
+
+extern "C" size_t ctts_batch_tile_map_ints(int nb0, int nb1, int M, int N) {
+  if (nb0 < 1 || nb1 < 1 || M < 1 || N < 1 || (long)nb0 * nb1 > 32767) return 0;
+  const BatchPlanGeom g = batch_map_geom(nb0, nb1, M, N, 1, 0, 0, 0, 0);
+  return batch_plan_fits(g) ? (size_t)(BATCH_PLAN_HDR + batch_plan_items(g)) : 0;
+}
+
+extern "C" int ctts_batch_tile_map(const int32_t* lens, int nb0, int nb1, int M, int N, int K, int lim_m, int lim_n, int lim_k,
+                                   int write_all, int32_t* tile_map, size_t map_ints, void* stream) {
+  CTTS_REQUIRE(lens && tile_map && K >= 0, "ctts_batch_tile_map: bad arguments");
+  const size_t need = ctts_batch_tile_map_ints(nb0, nb1, M, N);
+  CTTS_REQUIRE(need > 0, "ctts_batch_tile_map: %d x %d batches of [%d, %d] do not fit a plan (ctts_batch_tile_map_ints)", nb0, nb1, M, N);
+  CTTS_REQUIRE(map_ints >= need, "ctts_batch_tile_map: tile_map holds %zu int32, %zu needed", map_ints, need);
+  const BatchPlanGeom g = batch_map_geom(nb0, nb1, M, N, K, lim_m, lim_n, lim_k, write_all);
+  const long blocks = (batch_plan_items(g) + 255) / 256;
+  hipLaunchKernelGGL(batch_tile_map_kernel, dim3((unsigned)(blocks < 64 ? blocks : 64)), dim3(256), 0, (hipStream_t)stream, g, lens, tile_map);
+  CTTS_CHECK_LAUNCH("ctts_batch_tile_map");
+  return 0;
+}
+
 // ---- fp32-on-bf16-pipe kernels of this file (the CALLER chooses the arithmetic, per descriptor - ctts_gemm_desc.bf16_split: 0 = fp32
 // MFMA only, 1 = allowed, 2 = allowed below the size thresholds).  gemm_x6_kernel: large unbatched NT launches whose N is a multiple of
 // the 128-column tile.
@@ -1155,6 +1232,11 @@ static int x6_launch(const ctts_gemm_desc& d, hipStream_t st) {
   return 0;
 }
 
+// d.tile_map of a launch with per-batch length limits is a batch tile plan (ctts_batch_tile_map), not an m-tile schedule
+static bool batch_plan_given(const ctts_gemm_desc& d) {
+  return d.tile_map && d.tile_map != reinterpret_cast<const int32_t*>(1) && d.lens && (d.lim_m || d.lim_n || d.lim_k);
+}
+
 // What gemm_route decides for one descriptor: the launch, the queries and the split plan all read this and nothing else.
 struct GemmRoute {
   // kind; workgroup tile; split_k = K ranges that write partial matrices (the caller's, lowered until they fit; 1: none);
@@ -1175,7 +1257,7 @@ static void tile_plan(const ctts_gemm_desc& d, bool x6tn, GemmRoute& r) {
   // XCD-grouped order for scheduled launches: default 4 n-groups (XCD x: n-group x % 4, every second scheduled m-tile) - halves the
   // L2-miss traffic of the FFN conv (FETCH_SIZE 441 -> 195 MB per launch) at unchanged time; CTTS_TILE_GROUP=<g> overrides, 0 = off.
   static const int tile_group = ctts_env_int("CTTS_TILE_GROUP", -1);
-  if (tile_group != 0 && d.tile_map && d.tile_map != reinterpret_cast<const int32_t*>(1)) {
+  if (tile_group != 0 && d.tile_map && d.tile_map != reinterpret_cast<const int32_t*>(1) && !batch_plan_given(d)) {
     const int tn = (d.N + 63) / 64, tmn = (d.M + 63) / 64;
     const int g = tile_group > 0 ? tile_group : ((tn >= 8 && tn % 4 == 0) ? tn / 4 : 0);
     if (g > 0 && tn % g == 0) {
@@ -1217,7 +1299,7 @@ static void tile_plan(const ctts_gemm_desc& d, bool x6tn, GemmRoute& r) {
     if (force_tile == 128) { r.info.kind = CTTS_GEMM_BUF128; r.info.tile_m = r.info.tile_n = 128; }
     else if (k2 && (d.a_kc || (k2_tn && !d.b_kc)) && d.nb0 * d.nb1 == 1 && !d.lens && d.N >= 64 && d.M >= 256 && d.K >= k2_mink &&
              (long)((d.M + 63) / 64) * ((d.N + 63) / 64) * (d.split_k > 1 ? d.split_k : 1) <= k2) { r.info.kind = CTTS_GEMM_BUF_K2; r.info.tile_m = 32; }
-    else if (narrow && d.N <= 32 && d.M >= 256 && d.conv_T <= 0 && !d.tile_map && !r.natural_order && !d.row_lens) { r.info.kind = CTTS_GEMM_BUF_NARROW; r.info.tile_m = 128; r.info.tile_n = 32; }
+    else if (narrow && d.N <= 32 && d.M >= 256 && d.conv_T <= 0 && (!d.tile_map || batch_plan_given(d)) && !r.natural_order && !d.row_lens) { r.info.kind = CTTS_GEMM_BUF_NARROW; r.info.tile_m = 128; r.info.tile_n = 32; }
     else r.info.kind = CTTS_GEMM_BUF64;
   }
 #endif
@@ -1270,6 +1352,9 @@ static int gemm_validate(const ctts_gemm_desc* dp, ctts_gemm_desc& d) {
                "ctts_gemm: epi_bwd excludes bias, residual, rowscale, E and split-K, and needs Z when an activation is given");
   CTTS_REQUIRE(!d.E || (d.rowsub && d.split_k <= 1 && !d.bias && !d.act && d.p_drop == 0.f && !d.R && !d.rowscale && !d.Z),
                "ctts_gemm: the E/rowsub epilogue excludes bias, activation, dropout, residual, rowscale and split-K");
+  CTTS_REQUIRE(!batch_plan_given(d) || (!d.row_lens && d.split_k <= 1 && batch_plan_fits(batch_plan_geom(d, 64, 64, 1))),
+               "ctts_gemm: a batch tile plan (tile_map on a launch with length limits) excludes row_lens and split-K, and the batches "
+               "must fit one (ctts_batch_tile_map_ints)");
   return 0;
 }
 
@@ -1278,6 +1363,10 @@ static int gemm_plan(const ctts_gemm_desc* dp, ctts_gemm_desc& d, GemmRoute& r) 
   const int rc = gemm_validate(dp, d);
   if (rc != 0) return rc;
   gemm_route(d, r);
+  // only the 64 x 64 buffer kernel with per-batch limits follows a batch tile plan: on any other route the map would be read as an
+  // m-tile schedule, or not at all
+  CTTS_REQUIRE(!batch_plan_given(d) || r.info.kind == CTTS_GEMM_BUF64,
+               "ctts_gemm: a batch tile plan was given, but the launch does not run on the 64 x 64 buffer kernel (route kind %d)", r.info.kind);
   if (r.info.kind < CTTS_GEMM_X6TN || d.split_k <= 1) return 0;
   CTTS_REQUIRE(d.split_out || (d.sk_ws && d.sk_ws_bytes >= (int64_t)CTTS_WS_BYTES),
                "ctts_gemm: split_k > 1 needs the workspace (ctts_workspace_bytes() bytes, zero-filled once) in sk_ws - partial sums "

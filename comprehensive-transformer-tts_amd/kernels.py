@@ -291,6 +291,8 @@ def _gemm_desc(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, a_off=0
     if row_lens is not None:
         d.row_lens, d.row_T, d.row_halo = _p(row_lens), int(row_T), int(row_halo)
         d.tile_map = _p(tile_map)
+    elif lens is not None:
+        d.tile_map = _p(tile_map)          # a batch tile plan (batch_tile_map)
     d.E, d.rowsub = _p(E), _p(rowsub)
     d.epi_bwd = int(bool(epi_bwd))
     d.split_overwrite = int(bool(split_overwrite))
@@ -521,6 +523,20 @@ def row_tile_map(row_lens, row_T, row_halo, M):
     tm = torch.empty(1 + (M + 63) // 64, dtype=torch.int32, device=row_lens.device)
     lib = _lib.load()
     _lib.check(lib.ctts_row_tile_map(_p(row_lens), int(row_T), int(row_halo), int(M), _p(tm), _stream()), "ctts_row_tile_map")
+    return tm
+
+
+def batch_tile_map(lens, nb1, M, N, K, lim, write_all):
+    """Tile plan of the batched launches with per-batch limits `lens` [nb0], `lim`, nb1 inner batches and [M, N] outputs reduced over K,
+    `write_all` = their split_overwrite (include/ctts.h ctts_batch_tile_map): pass it as gemm(..., tile_map=).  None when these
+    batches do not fit a plan: launch without one."""
+    lib = _lib.load()
+    n = lib.ctts_batch_tile_map_ints(int(lens.numel()), int(nb1), int(M), int(N))
+    if n == 0:
+        return None
+    tm = torch.empty(n, dtype=torch.int32, device=lens.device)
+    _lib.check(lib.ctts_batch_tile_map(_p(lens), int(lens.numel()), int(nb1), int(M), int(N), int(K), int(lim[0]), int(lim[1]), int(lim[2]),
+                                       int(bool(write_all)), _p(tm), n, _stream()), "ctts_batch_tile_map")
     return tm
 
 

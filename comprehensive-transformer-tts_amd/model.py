@@ -198,7 +198,7 @@ class FFTBlocks(nn.Module):
                 x = ops.stage_cut(x, f"{self._cut_prefix}.{li}")
             h, xr = ops.layer_norm_res(x, op.layer_norm1.weight, op.layer_norm1.bias, 1e-12)
             qkv = ops.linear(h, op.self_attn.in_proj_weight, pad_rows=pr)
-            a = ops.self_attention(qkv, lens, self.num_heads)
+            a = ops.self_attention(qkv, lens, self.num_heads, pad_rows=pr)
             x = ops.linear(a, op.self_attn.out_proj.weight, None, residual=xr, rowscale=nonpad, p_drop=p, drop=drop, pad_rows=pr)
             # the FFN convolution runs on the plane kernel at the decoder's size: LN2 writes its operand planes in the same launch
             h, xr = ops.layer_norm_res(x, op.layer_norm2.weight, op.layer_norm2.bias, 1e-12,

@@ -609,12 +609,31 @@ class PadRows:
     def __init__(self, lens, T):
         self.lens, self.T = lens, int(T)
         self._maps = {}
+        self._batch_maps = {}
 
     def tile_map(self, halo, M):
         key = (int(halo), int(M))
         if key not in self._maps:
             self._maps[key] = K.row_tile_map(self.lens, self.T, halo, M)
         return self._maps[key]
+
+
+    def batch_map(self, A, B, Cout, lim, write_all):
+        """The tile plan (kernels.batch_tile_map) of the batched launch `Cout = A @ B` limited by self.lens, or None where the launch
+        keeps the plain order: built at the first launch of a geometry and shared by every launch of the stack's forward and backward
+        with the same output shape, limits and write_all - whatever the operand layout.  None: the batches fit no plan, the launch
+        is not routed to the kernel that follows one, or it has at most _BATCH_ORDER_MIN_ITEMS tiles."""
+        key = (tuple(Cout.shape), int(A.shape[-1]), tuple(lim), bool(write_all))
+        if key not in self._batch_maps:
+            plan = None
+            nb1, (M, N), Kd = (Cout.shape[1] if Cout.dim() == 4 else 1), Cout.shape[-2:], A.shape[-1]
+            if Cout.is_cuda and Cout.dim() >= 3 and Cout.shape[0] * nb1 * -(-M // 64) * -(-N // 64) > _BATCH_ORDER_MIN_ITEMS:
+                args, views = K.gemm_views(A, B, Cout, lens=self.lens)
+                route = K.gemm_route(*args, **views, lens=self.lens, lim=lim, split_overwrite=write_all)
+                if route.kind == "buf64":
+                    plan = K.batch_tile_map(self.lens, nb1, M, N, Kd, lim, write_all)
+            self._batch_maps[key] = plan
+        return self._batch_maps[key]
 
 
 def _pad_rows(pad_rows):
@@ -774,6 +793,12 @@ def layer_norm(x, gamma, beta, eps, rowscale=None, p_drop=0.0, drop=None):
 # tuning knob; 1 = off (default since round 4: with the ordered reduce launch a 2-way split of the [T, T] x [T, dh] products costs more
 # than the under-filled launch it avoids - fs2 step 23.73 -> 23.50 ms, same box)
 _ATTN_SPLIT_K = int(_os.environ.get("CTTS_ATTN_SPLIT_K", "1"))
+# A/B switch: "natural" = the attention products launch in plain block order (tile x batch), as before the length-balanced tile plans
+# (csrc/batch_plan.h).  Results are bit-identical either way.
+_BATCH_ORDER = _os.environ.get("CTTS_BATCH_ORDER", "balanced")
+# launches with no more tiles than this keep the plain order: the encoder-size products (T = 128: 128 tiles for 256 CUs) give every
+# workgroup a CU of its own in any order, a plan would only add its build launch
+_BATCH_ORDER_MIN_ITEMS = 256
 
 
 def _attn_split_k(nbatch, T, dh):
@@ -840,29 +865,38 @@ class _SelfAttention(torch.autograd.Function):
     multiplies by the non-pad mask anyway, transformer_fs2.py:190)."""
 
     @staticmethod
-    def forward(ctx, qkv, lens, n_heads):
+    def _bgemm(pr, A, B, Cout, lens, lim, split_k=1, split_overwrite=False, **kw):
+        """one attention product, in the length-balanced tile order where `pr` (a PadRows of lens, or None) has a plan for it"""
+        plan = pr.batch_map(A, B, Cout, lim, split_overwrite) if (pr is not None and split_k <= 1) else None
+        return K.bgemm(A, B, Cout, lens=lens, lim=lim, split_k=split_k, split_overwrite=split_overwrite, tile_map=plan, **kw)
+
+    @staticmethod
+    def forward(ctx, qkv, lens, n_heads, pad_rows=None):
         qkv = qkv.contiguous()
         B, T, C3 = qkv.shape
         C = C3 // 3
         dh = C // n_heads
+        # the tile plans of the products: the caller's PadRows keeps them for all layers of its stack, forward and backward
+        pr = None if _BATCH_ORDER == "natural" else (pad_rows if pad_rows is not None else PadRows(lens, T))
         q, k, v = _heads(qkv, n_heads, 3)
         S = torch.empty(B, n_heads, T, T, dtype=torch.float32, device=qkv.device)
         # S[q,key] = scale * sum_d Q[q,d] K[key,d]
-        K.bgemm(q, k.transpose(-1, -2), S, lens=lens, lim=(1, 1, 0), alpha=dh ** -0.5)
+        _SelfAttention._bgemm(pr, q, k.transpose(-1, -2), S, lens, (1, 1, 0), alpha=dh ** -0.5)
         K.softmax_fwd(S, lens, B, n_heads, T)
         sk = _attn_split_k(B * n_heads, T, dh)
         # "write everything" (split_overwrite): the query rows >= len are written as zeros by the launch itself - no fill launch
         out = torch.empty(B, T, C, dtype=torch.float32, device=qkv.device)
         # O[q,d] = sum_key P[q,key] V[key,d]
-        K.bgemm(S, v, _heads(out, n_heads)[0], lens=lens, lim=(1, 0, 1), split_k=sk, split_overwrite=True)
+        _SelfAttention._bgemm(pr, S, v, _heads(out, n_heads)[0], lens, (1, 0, 1), split_k=sk, split_overwrite=True)
         ctx.save_for_backward(qkv, S, lens, out)
         ctx.n_heads = n_heads
+        ctx.pad_rows = pr
         return out
 
     @staticmethod
     def backward(ctx, dO):
         qkv, P, lens, O = ctx.saved_tensors
-        H = ctx.n_heads
+        H, pr, bg = ctx.n_heads, ctx.pad_rows, _SelfAttention._bgemm
         dO = dO.contiguous()
         B, T, C3 = qkv.shape
         dh = C3 // 3 // H
@@ -871,24 +905,25 @@ class _SelfAttention(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)            # the three launches below write all of it ("write everything": zeros beyond each utterance's length)
         (q, k, v), (dq, dk, dv), (dOh,) = _heads(qkv, H, 3), _heads(dqkv, H, 3), _heads(dO, H)
         # dV[key,d] = sum_q P[q,key] dO[q,d]
-        K.bgemm(P.transpose(-1, -2), dOh, dv, lens=lens, lim=(1, 0, 1), split_k=sk, split_overwrite=True)
+        bg(pr, P.transpose(-1, -2), dOh, dv, lens, (1, 0, 1), split_k=sk, split_overwrite=True)
         # dS[q,key] = P * (dO V^T - D),  D[q] = sum_key dP P = sum_d dO[q,d] O[q,d]: the softmax backward rides in the epilogue of the
         # dP GEMM (one read of P) instead of a separate pass that re-reads P and dP and rewrites dS
         Dv = K.rowdot_heads(dO, O, H)
         dP = torch.empty_like(P)
-        K.bgemm(dOh, v.transpose(-1, -2), dP, lens=lens, lim=(1, 1, 0), E=P, rowsub=Dv)
+        bg(pr, dOh, v.transpose(-1, -2), dP, lens, (1, 1, 0), E=P, rowsub=Dv)
         # dQ[q,d] = scale * sum_key dS[q,key] K[key,d]
-        K.bgemm(dP, k, dq, lens=lens, lim=(1, 0, 1), alpha=scale, split_k=sk, split_overwrite=True)
+        bg(pr, dP, k, dq, lens, (1, 0, 1), alpha=scale, split_k=sk, split_overwrite=True)
         # dK[key,d] = scale * sum_q dS[q,key] Q[q,d]
-        K.bgemm(dP.transpose(-1, -2), q, dk, lens=lens, lim=(1, 0, 1), alpha=scale, split_k=sk, split_overwrite=True)
-        return dqkv, None, None
+        bg(pr, dP.transpose(-1, -2), q, dk, lens, (1, 0, 1), alpha=scale, split_k=sk, split_overwrite=True)
+        return dqkv, None, None, None
 
 
-def self_attention(qkv, lens_i32, n_heads):
+def self_attention(qkv, lens_i32, n_heads, pad_rows=None):
+    """pad_rows: the PadRows of (lens_i32, T) of the calling stack, which then keeps the tile plans of the products for all its layers"""
     want = _FUSED_ATTN if _FUSED_ATTN is not None else not (torch.is_grad_enabled() and qkv.requires_grad)
     if want and K.mha_supported(qkv.shape[-1] // 3, n_heads):
         return _FusedSelfAttention.apply(qkv, lens_i32, n_heads)
-    return _SelfAttention.apply(qkv, lens_i32, n_heads)
+    return _SelfAttention.apply(qkv, lens_i32, n_heads, pad_rows)
 
 
 class _LRGather(torch.autograd.Function):

@@ -80,7 +80,12 @@ typedef struct ctts_gemm_desc {
    * tile_map[1..] = m-tile indices, active ones first.  Workgroup b then works on m-tile tile_map[1 + b / tiles_n] and n-tile
    * b % tiles_n: the active tiles occupy the first workgroup ids, so the hardware's round-robin placement spreads them evenly over
    * the 8 XCDs (a fixed permutation leaves a +-10 % imbalance of active tiles per XCD), and each XCD only sees tiles_n / 8 weight
-   * panels.  NULL = built-in scrambled order. */
+   * panels.  NULL = built-in scrambled order.
+   * On a launch with per-batch length limits (lens and a lim_*; no row_lens, split_k <= 1) tile_map is instead a BATCH TILE PLAN
+   * (ctts_batch_tile_map, built for the same nb0, nb1, M, N, lim_* and split_overwrite): the workgroup with linear id
+   * blockIdx.z * gridDim.x + blockIdx.x works on the (batch, tile) the plan lists there - active tiles first, dealt evenly by work
+   * over the compute units.  Only the 64 x 64 buffer kernel follows one (ctts_gemm refuses it on any other route); a plan built for
+   * another geometry is not followed (plain order).  Results do not depend on it.  NULL = plain order. */
   const int32_t* tile_map;
   /* with tile_map: n-tiles per XCD group (0 = plain order).  g > 0 (tiles_n % g == 0, tiles_n / g in {1,2,4,8}): XCD x works on the g
    * n-tiles of group x % (tiles_n/g) and on every (8*g/tiles_n)-th scheduled m-tile - trades weight-panel against activation-tile
@@ -258,6 +263,17 @@ int ctts_epilogue_bwd(const float* dy, const float* rowscale, const float* z, fl
 /* m-tile schedule for padded-row skipping (see ctts_gemm_desc.tile_map): a 64-row tile is inactive when all its rows (b,t) belong to one
  * utterance b and t >= row_lens[b] + row_halo.  tile_map: 1 + ceil(M/64) int32. */
 int ctts_row_tile_map(const int32_t* row_lens, int row_T, int row_halo, int M, int32_t* tile_map, void* stream);
+
+/* Batch tile plan for launches with per-batch length limits (see ctts_gemm_desc.tile_map; csrc/batch_plan.h): a permutation of the
+ * (batch, 64 x 64 tile) items of nb0 x nb1 batches of [M, N] outputs, built on the device from lens [nb0] (no host sync: capturable;
+ * rebuild it when the lengths change).  Active tiles (inside the batch's limits) come first, sorted by their K-blocks and dealt in snake
+ * order over the compute units; then, with write_all (the launch's split_overwrite), the tiles the launch zero-fills.  tile_map[0] =
+ * active tiles, [1] = listed tiles, [2] = all tiles, [3] = geometry key, then one item per workgroup id.  One plan serves every launch
+ * with the same nb0, nb1, M, N, K, lim_* and write_all, whatever its operand layout.
+ * ctts_batch_tile_map_ints: the int32 the plan takes, or 0 when these batches do not fit one (launch without a plan then). */
+size_t ctts_batch_tile_map_ints(int nb0, int nb1, int M, int N);
+int ctts_batch_tile_map(const int32_t* lens, int nb0, int nb1, int M, int N, int K, int lim_m, int lim_n, int lim_k, int write_all,
+                        int32_t* tile_map, size_t map_ints, void* stream);
 
 /* Conv1d weight repack: w[Cout][Cin][K] (reference nn.Conv1d layout) ->
  *   mode 0: wf[Cout][K][Cin]                 (forward implicit-GEMM B operand)

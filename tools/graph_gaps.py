@@ -1,6 +1,6 @@
 """Gaps between kernels under hipGraph replay: from a rocprofv3 --kernel-trace database of `bench.py` (graph mode), take the last
 replayed step (the kernels between the last two launches of adam_kernel) and compare the sum of kernel durations with the span from the
-first kernel's start to the last kernel's end.   python tools/graph_gaps.py <results.db>"""
+first kernel's start to the last kernel's end.   python tools/graph_gaps.py <results.db> [rows of the kernel table, default 45]"""
 import sqlite3, sys
 
 db = sqlite3.connect(sys.argv[1])
@@ -30,5 +30,5 @@ for n, s, e in seg:
 small = sum(1 for _, s, e in seg if e - s < 10000), sum((e - s) / 1e3 for _, s, e in seg if e - s < 10000)
 print(f"\nlast step: kernels shorter than 10 us: {small[0]} launches, {small[1]/1e3:.3f} ms")
 print("| ms | calls | avg us | kernel |")
-for k, (c, t) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:45]:
+for k, (c, t) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:int(sys.argv[2]) if len(sys.argv) > 2 else 45]:
     print(f"| {t/1e3:6.3f} | {c:4d} | {t/c:7.1f} | {k} |")
