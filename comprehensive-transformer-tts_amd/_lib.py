@@ -230,6 +230,11 @@ _SIGNATURES = {
     "ctts_stoi": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp],
     "ctts_si_sdr": [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp],
     "ctts_mr_stft": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
+    "ctts_speaker_frames": [C.c_int],
+    "ctts_speaker_span": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp],
+    "ctts_speaker_fbank": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "ctts_conv2d_nhwc": [_vp, _vp, _vp, _vp, _vp] + [C.c_int] * 7 + [_f32, _f32, _vp, _vp],
+    "ctts_speaker_head": [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
     "ctts_comm_unique_id": [_vp],
     "ctts_comm_create": [C.POINTER(_vp), _i32, _i32, _vp],
     "ctts_comm_destroy": [_vp],
@@ -243,7 +248,7 @@ EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["ctts_last_error", "ctts_version"
                                                "ctts_pitch_track_workspace_bytes", "ctts_trim_silence_workspace_bytes",
                                                "ctts_dtw_workspace_bytes", "ctts_loudness_workspace_bytes", "ctts_stoi_workspace_bytes",
                                                "ctts_si_sdr_workspace_bytes", "ctts_mr_stft_workspace_bytes",
-                                               "ctts_batch_tile_map_ints"])
+                                               "ctts_batch_tile_map_ints", "ctts_conv2d_nhwc_workspace_bytes"])
 ADAM_STATE_FLOATS = 3 + 2048          # CTTS_ADAM_STATE_FLOATS of include/ctts.h
 ABI_VERSION = 2                       # ctts_version() of the library this binding was written for
 
@@ -308,6 +313,8 @@ def load():
     lib.ctts_mr_stft_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ctts_batch_tile_map_ints.restype = C.c_size_t
     lib.ctts_batch_tile_map_ints.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.ctts_conv2d_nhwc_workspace_bytes.restype = C.c_size_t
+    lib.ctts_conv2d_nhwc_workspace_bytes.argtypes = [C.c_int] * 6
     lib.ctts_relmha_workspace_floats.restype = C.c_size_t
     lib.ctts_relmha_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int]
     _lib = lib

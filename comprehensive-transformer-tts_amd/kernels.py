@@ -2165,3 +2165,121 @@ def mr_stft(ref, syn, lens, window, n_fft, hop):
     _lib.check(lib.ctts_mr_stft(_p(ref), _p(syn), _p(lens), _p(window), _p(out), _p(frames), B, N, n_fft, hop, win, _p(ws), _stream()),
                "ctts_mr_stft")
     return out, frames
+
+
+# ---- speaker embeddings: voice span, filterbank features, NHWC convolution, head (csrc/speaker.hip) ------------------------------------
+SPEAKER_NFILT, SPEAKER_BINS = 64, 66
+CONV_K5S2_SAME, CONV_K3S1 = 0, 1
+
+
+def speaker_frames(span):
+    """frames of 551 samples at step 221 (the tail zero-padded) of a span of `span` samples; 0 for an empty span"""
+    return int(_lib.load().ctts_speaker_frames(int(span)))
+
+
+def _wav_batch(wav, lens, what):
+    if not torch.is_tensor(wav) or wav.dim() != 2:
+        raise _lib.CttsError(f"{what}: expected wav [B, N]")
+    _p(wav)
+    _al4(_f32c(wav, "wav"), "wav")
+    B, N = wav.shape
+    if B < 1 or N < 1 or B > 65535 or N > 1 << 30:
+        raise _lib.CttsError(f"{what}: need 1 .. 65535 utterances of 1 .. 2^30 samples, got {tuple(wav.shape)}")
+    if lens is not None:
+        _lens_i32(lens, B, what)
+    return B, N
+
+
+def _i32_vec(t, n, name, what):
+    _p(t)
+    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise _lib.CttsError(f"{what}: {name} must be {n} contiguous int32 words on the device")
+    return t
+
+
+def speaker_span(wav, lens):
+    """wav [B,N] float32, lens int32 [B] -> (first, last, n_frames, valid) int32 [B]: the span x[first:last] above the 95th percentile of
+    |x|, its fbank frame count and whether it holds a sample"""
+    B, N = _wav_batch(wav, lens, "speaker_span")
+    first, last, frames, valid = (torch.empty(B, dtype=torch.int32, device=wav.device) for _ in range(4))
+    _lib.check(_lib.load().ctts_speaker_span(_p(wav), _p(lens), _p(first), _p(last), _p(frames), _p(valid), B, N, _stream()),
+               "ctts_speaker_span")
+    return first, last, frames, valid
+
+
+def speaker_fbank(wav, first, last, valid, bins, out_frames, offsets=None, centre=False):
+    """wav [B,N] float32 and the span of `speaker_span`, bins int32 [66] -> normalised filterbank features float32 [B, out_frames, 64];
+    row j is frame r + j with r = offsets[b], else the centre crop when `centre`, else 0"""
+    B, N = _wav_batch(wav, None, "speaker_fbank")
+    for t, name in ((first, "first"), (last, "last"), (valid, "valid")):
+        _i32_vec(t, B, name, "speaker_fbank")
+    _i32_vec(bins, SPEAKER_BINS, "bins", "speaker_fbank")
+    if offsets is not None:
+        _i32_vec(offsets, B, "offsets", "speaker_fbank")
+    out_frames = int(out_frames)
+    if out_frames < 1:
+        raise _lib.CttsError(f"speaker_fbank: out_frames must be >= 1, got {out_frames}")
+    out = torch.empty(B, out_frames, SPEAKER_NFILT, dtype=torch.float32, device=wav.device)
+    _lib.check(_lib.load().ctts_speaker_fbank(_p(wav), _p(first), _p(last), _p(valid), _p(bins), _p(offsets), _p(out), B, N, out_frames,
+                                              1 if centre else 0, _stream()), "ctts_speaker_fbank")
+    return out
+
+
+def conv2d_nhwc_out_hw(H, W, geom):
+    s = 2 if geom == CONV_K5S2_SAME else 1
+    return -(-H // s), -(-W // s)
+
+
+def conv2d_nhwc(x, w, bias, geom, lo, hi, res=None, out=None):
+    """x [B,H,W,Cin] float32 NHWC, w [k,k,Cin,Cout], bias [Cout] -> clip(conv + bias) [B,Ho,Wo,Cout], or clip(clip(conv + bias) + res)
+    with a residual shaped like the output; geom CONV_K5S2_SAME (5 x 5, stride 2, TF 'same') or CONV_K3S1 (3 x 3, stride 1, pad 1)"""
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise _lib.CttsError("conv2d_nhwc: expected x [B, H, W, Cin]")
+    for t, name in ((x, "x"), (w, "w"), (bias, "bias")):
+        _p(t)
+        _f32c(t, name)
+    if geom not in (CONV_K5S2_SAME, CONV_K3S1):
+        raise _lib.CttsError(f"conv2d_nhwc: unknown geometry {geom}")
+    B, H, W, Cin = x.shape
+    k = 5 if geom == CONV_K5S2_SAME else 3
+    if w.dim() != 4 or tuple(w.shape[:3]) != (k, k, Cin):
+        raise _lib.CttsError(f"conv2d_nhwc: w {tuple(w.shape)} is not [{k}, {k}, {Cin}, Cout]")
+    Cout = w.shape[3]
+    if tuple(bias.shape) != (Cout,):
+        raise _lib.CttsError(f"conv2d_nhwc: bias {tuple(bias.shape)} is not [{Cout}]")
+    Ho, Wo = conv2d_nhwc_out_hw(H, W, geom)
+    shape = (B, Ho, Wo, Cout)
+    if res is not None:
+        _p(res)
+        if tuple(_f32c(res, "res").shape) != shape:
+            raise _lib.CttsError(f"conv2d_nhwc: res {tuple(res.shape)} does not match the output {shape}")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _p(out)
+        if tuple(_f32c(out, "out").shape) != shape:
+            raise _lib.CttsError(f"conv2d_nhwc: out {tuple(out.shape)} does not match {shape}")
+    lib = _lib.load()
+    nbytes = lib.ctts_conv2d_nhwc_workspace_bytes(B, H, W, Cin, Cout, geom)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    _lib.check(lib.ctts_conv2d_nhwc(_p(x), _p(w), _p(bias), _p(res), _p(out), B, H, W, Cin, Cout, geom, 0 if res is None else 1,
+                                    float(lo), float(hi), _p(ws), _stream()), "ctts_conv2d_nhwc")
+    return out
+
+
+def speaker_head(x, w, bias, valid=None):
+    """x [B,T,F] float32, w [F,E], bias [E] -> the L2-normalised affine image of the time mean, float32 [B,E]; zeros where valid == 0"""
+    if not torch.is_tensor(x) or x.dim() != 3:
+        raise _lib.CttsError("speaker_head: expected x [B, T, F]")
+    for t, name in ((x, "x"), (w, "w"), (bias, "bias")):
+        _p(t)
+        _f32c(t, name)
+    B, T, F = x.shape
+    if w.dim() != 2 or w.shape[0] != F or tuple(bias.shape) != (w.shape[1],):
+        raise _lib.CttsError(f"speaker_head: w {tuple(w.shape)} / bias {tuple(bias.shape)} do not fit x {tuple(x.shape)}")
+    E = w.shape[1]
+    if valid is not None:
+        _i32_vec(valid, B, "valid", "speaker_head")
+    out = torch.empty(B, E, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().ctts_speaker_head(_p(x), _p(w), _p(bias), _p(valid), _p(out), B, T, F, E, _stream()), "ctts_speaker_head")
+    return out

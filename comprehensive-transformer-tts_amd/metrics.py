@@ -323,3 +323,14 @@ def summarize_waveform(result):
             mean = np.where(ok, a, 0.0).sum(axis=0) / n
         out[name] = {"mean": mean.tolist(), "count": n.tolist()}
     return out
+
+
+def speaker_similarity(ref, ref_lens, syn, syn_lens, embedder, source_rate=None):
+    """Cosine of the DeepSpeaker embeddings of `ref` and `syn` per pair, float32 [B] on the device: the speaker-similarity figure of
+    multi-speaker synthesis.  ref [B, N1], syn [B, N2] float32 at 22050 Hz (or at `source_rate`), lengths as in `speaker.DeepSpeakerEmbedder`
+    (centre crop).  The embeddings are unit vectors, so the cosine is their dot product; a pair with an invalid side (no voice span) gives 0."""
+    a = embedder(ref, ref_lens, source_rate=source_rate)["embedding"]
+    b = embedder(syn, syn_lens, source_rate=source_rate)["embedding"]
+    if a.shape != b.shape:
+        raise CttsError(f"speaker_similarity: {a.shape[0]} reference and {b.shape[0]} synthesised utterances")
+    return (a.double() * b.double()).sum(1).float()

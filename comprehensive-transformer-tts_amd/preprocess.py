@@ -306,3 +306,32 @@ def process_batch_loudness(wavs, n_phones, stft, preprocess_config, loudness=-22
         wav[i, :lens[i]] = w
     out = normalize_loudness(wav, lens, stft.sampling_rate, target=float(loudness), peak_limit=True, out=wav)[0]
     return process_batch([out[i, :n] for i, n in enumerate(lens)], n_phones, stft, preprocess_config, spans=spans)
+
+
+def speaker_embeddings(wavs, speakers, embedder, source_rate=None):
+    """The speaker-embedding files of the reference's preprocessor (preprocessor.py:246-263, 376): wavs - a sequence of 1-D float device
+    tensors at 22050 Hz (or at `source_rate`), speakers - one speaker name per utterance, embedder - a `speaker.DeepSpeakerEmbedder`.
+    Returns (per_utterance, per_speaker), numpy on the host: per_utterance = {"embedding" float32 [B,512] (zero rows where `valid` is 0),
+    "valid" int32 [B]}; per_speaker = {speaker: the mean of the speaker's valid embeddings, float32 [512]} - what the reference saves as
+    `{speaker}-spker_embed.npy`.  A speaker without a valid utterance is left out."""
+    if len(wavs) == 0:
+        raise ValueError("speaker_embeddings: empty batch")
+    if len(speakers) != len(wavs):
+        raise ValueError(f"speaker_embeddings: {len(speakers)} speakers for {len(wavs)} utterances")
+    for w in wavs:
+        if not torch.is_tensor(w) or not w.is_cuda:
+            raise CttsError("speaker_embeddings computes on the MI355X: pass device tensors - no CPU fallback exists")
+        if w.dim() != 1 or w.numel() < 1:
+            raise ValueError(f"speaker_embeddings: each utterance is a non-empty 1-D tensor, got {tuple(w.shape)}")
+    lens = [int(w.numel()) for w in wavs]
+    wav = torch.zeros(len(wavs), max(lens), dtype=torch.float32, device=wavs[0].device)
+    for i, w in enumerate(wavs):
+        wav[i, :lens[i]] = w
+    res = embedder(wav, lens, source_rate=source_rate)
+    emb, valid = res["embedding"].cpu().numpy(), res["valid"].cpu().numpy()
+    per_speaker = {}
+    for spk in dict.fromkeys(speakers):
+        rows = [i for i, s in enumerate(speakers) if s == spk and valid[i]]
+        if rows:
+            per_speaker[spk] = emb[rows].astype(np.float64).mean(0).astype(np.float32)
+    return {"embedding": emb, "valid": valid}, per_speaker

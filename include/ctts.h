@@ -1002,6 +1002,45 @@ size_t ctts_mr_stft_workspace_bytes(int B, int N, int hop, int win);
 int ctts_mr_stft(const float* ref, const float* syn, const int32_t* lens, const double* window, double* out, int32_t* frames, int B, int N,
                  int n_fft, int hop, int win, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Speaker embeddings on the device (csrc/speaker.hip): the DeepSpeaker front end and ResCNN.  The definitions are
+ * those of the ctts_amd.speaker docstring, pinned by the float64 restatement in tests/speaker_restate.py; PARITY with the TF model and
+ * python_speech_features is UNPINNED (neither is installed where this project is built).  Stream-ordered, caller-allocated, no host
+ * sync, no float atomics: bit-reproducible, and a row's result does not depend on the other rows.  Every output element is written.
+ *
+ * Span: wav [B][N] fp32, lens int32 [B] (clamped to [0, N]; samples at and beyond lens[b] are never read).  thr = the 95th percentile of
+ * |x| with linear interpolation, formed in double from the two fp32 order statistics the way numpy forms it; first / last = the lowest /
+ * highest index with |x| > thr in double (both 0 when there is none); valid = last - first >= 1; n_frames = the frame count of the span
+ * x[first:last] (frames of 551 at step 221, the tail zero-padded: 1 up to 551 samples, else 1 + ceil((L - 551) / 221)), 0 when invalid.
+ * The frame-count query returns that count for a span of L samples.
+ *
+ * Fbank: out [B][out_frames][64] fp32.  Row j holds frame r + j of the span: pre-emphasis 0.97 inside the span, rectangular window,
+ * |rfft(frame, 1024)|^2 / 1024, the 64 triangular filters on `bins` (int32 [66], non-decreasing in [0, 512]), exact zeros replaced by
+ * 2^-52, then (v - mean) / max(std, 1e-12) over the 64 filters (population std); computed in double, rounded once.  r = offsets[b]
+ * (int32 [B]) when given, else (n_frames - out_frames) / 2 when `centre`, else 0; clamped to [0, max(n_frames - out_frames, 0)].  Rows
+ * at and beyond n_frames, and every row of an invalid utterance, are zeros.
+ *
+ * Conv: NHWC fp32 x [B][H][W][Cin] -> out [B][Ho][Wo][Cout], weights [kh][kw][Cin][Cout] (the Keras layout), as an implicit GEMM on the
+ * exact fp32 MFMA - no patch matrix in memory.  geom 0: 5 x 5, stride 2, TF 'same' (Ho = ceil(H / 2); total = max((Ho - 1) 2 + 5 - H, 0)
+ * cells of padding, total / 2 of them before: even sizes pad (1, 2), odd ones (2, 2));  geom 1: 3 x 3, stride 1, pad 1.  mode 0:
+ * clip(acc + bias);  mode 1: clip(clip(acc + bias) + res) with res shaped like out;  clip(v) = min(max(v, lo), hi).  DOMAIN: B, H, W >= 1,
+ * Cin 1 or a multiple of 64, Cout a multiple of 64, fewer than 2^31 elements in x and in out, 16-byte aligned pointers.  Shapes with few
+ * output tiles split K; their partial tiles go through `workspace` (size from the query, 0 when none is needed; no initialisation) and
+ * are added in index order.
+ *
+ * Head: x [B][T][F] -> out [B][E]: the mean over T, times w [F][E] plus bias [E], divided by max(its L2 norm, 1e-12); sums in double.
+ * Rows with valid[b] == 0 are zeros (valid may be NULL).  DOMAIN: F + E <= 7168. */
+int ctts_speaker_frames(int span);
+int ctts_speaker_span(const float* wav, const int32_t* lens, int32_t* first, int32_t* last, int32_t* n_frames, int32_t* valid, int B, int N,
+                      void* stream);
+int ctts_speaker_fbank(const float* wav, const int32_t* first, const int32_t* last, const int32_t* valid, const int32_t* bins,
+                       const int32_t* offsets, float* out, int B, int N, int out_frames, int centre, void* stream);
+size_t ctts_conv2d_nhwc_workspace_bytes(int B, int H, int W, int Cin, int Cout, int geom);
+int ctts_conv2d_nhwc(const float* x, const float* w, const float* bias, const float* res, float* out, int B, int H, int W, int Cin, int Cout,
+                     int geom, int mode, float lo, float hi, void* workspace, void* stream);
+int ctts_speaker_head(const float* x, const float* w, const float* bias, const int32_t* valid, float* out, int B, int T, int F, int E,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
