@@ -12,8 +12,9 @@ area normalisation, htk=False), which the reference pulls from a third-party dep
 running on THIS restated basis (oracle/ref_import.py stubs librosa with it), so G8 pins the STFT / magnitude / log arithmetic against
 the reference, but not the basis.  What pins the basis is tests/test_mel_basis_cpu.py: the Slaney mel scale against the worked examples
 of librosa's own documentation (hz_to_mel / mel_to_hz / mel_frequencies(n_mels=40), all 40 values), and the triangle construction with
-the 2 / (f[i+2] - f[i]) area normalisation against its published definition.  Swap in librosa's array (`stft.mel_basis.copy_(...)`)
-where it is available.
+the 2 / (f[i+2] - f[i]) area normalisation against its published definition.  Swap in librosa's array (`stft.mel_basis.copy_(...)`,
+`stft.set_mel_basis(...)` or `load_state_dict`) where it is available: both paths follow the buffer - what they derive from it (the
+highest bin with weight, the padded copy, the FFT kernel's workspace) is rebuilt at the next call (TacotronSTFT._sync_filterbank).
 
 Griffin-Lim (reference audio/stft.py:22-134 `STFT`, audio/audio_processing.py `griffin_lim` / `window_sumsquare` /
 `dynamic_range_*`, audio/tools.py:18-34 `inv_mel_spec`): `STFT.transform` / `inverse` and every Griffin-Lim iteration run on
@@ -279,8 +280,9 @@ class TacotronSTFT(nn.Module):
         self.stft_fn = STFT(filter_length, hop_length, win_length)      # non-persistent buffers only: state_dict stays ['mel_basis']
         self._fft_ws = None          # device workspace of the FFT kernel (twiddles, transposed filterbank), built on first use
         self.use_fft = filter_length == 1024 and n_mel_channels <= 96
-        nz = np.nonzero(np.abs(mel).sum(0))[0]
-        self._kmax = int(nz.max()) + 1 if len(nz) else 0       # bins above fmax carry no filter weight: not kept on chip
+        # what is derived from the filterbank (_kmax, _mel_basis_padded, _fft_ws) follows the `mel_basis` buffer: see _sync_filterbank
+        self._basis_key = None
+        self._kmax_value = 0
         self._range = None           # range check of the FFT path: (flag in pinned host memory, event of the last launch)
         # strict_range = True (default): the reference's contract - the assertion is raised by the SAME call that was handed the bad
         # waveform (one event wait per call instead of the reference's two reductions + sync).  False: the training / bulk-extraction
@@ -318,6 +320,9 @@ class TacotronSTFT(nn.Module):
         bits = int(host[0]) & 0xFFFFFFFF
         if bits:
             host.zero_()
+            if bits == 0x7FC0004B:                         # include/ctts.h CTTS_MEL_FLAG_KMAX
+                raise RuntimeError("TacotronSTFT.mel_spectrogram: the filterbank of the kernel workspace carries weight above the kmax of "
+                                   "the launch - the mel rows of those filters are NaN")
             val = np.array([bits], dtype=np.uint32).view(np.float32)[0]
             raise AssertionError(f"TacotronSTFT.mel_spectrogram: waveform outside [-1, 1] (largest |sample| {val})  [audio/stft.py:177-178]")
 
@@ -325,14 +330,54 @@ class TacotronSTFT(nn.Module):
         """block until the range flag of every mel_spectrogram call issued so far has arrived and raise if a waveform left [-1, 1]"""
         self._raise_if_out_of_range(wait=True)
 
+    def _sync_filterbank(self):
+        """`mel_basis` is the module's state: `stft.mel_basis.copy_(array)`, `load_state_dict` and `.to(device)` all change it.  Everything
+        derived from it - the highest bin with filter weight (_kmax), the padded copy of the DFT-as-GEMM path and the FFT kernel's
+        workspace - is rebuilt here whenever the buffer's (_version, device, data_ptr) differs from the one it was derived from."""
+        mel = self.mel_basis
+        key = (mel._version, mel.device, mel.data_ptr())
+        if key == self._basis_key:
+            return
+        if mel.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("TacotronSTFT (ctts_amd): call the module once after changing mel_basis (or moving it) before capturing a "
+                               "graph - what it derives from the filterbank is rebuilt by kernel launches and a host read, which a "
+                               "capture would only record")
+        mel = mel.detach()
+        if tuple(mel.shape) != (self.n_mel_channels, self.nbins):
+            raise ValueError(f"TacotronSTFT: mel_basis must stay [{self.n_mel_channels}, {self.nbins}], got {tuple(mel.shape)}")
+        nz = torch.nonzero(mel.abs().sum(0) != 0)          # NaN weights count as weight
+        self._kmax_value = int(nz.max()) + 1 if nz.numel() else 0      # bins above fmax carry no filter weight: not kept on chip
+        padded = torch.zeros(self.n_mel_channels, (self.nbins + 3) // 4 * 4, dtype=torch.float32, device=mel.device)
+        padded[:, :self.nbins] = mel
+        self._mel_basis_padded = padded
+        self._fft_ws = None                                # rebuilt by _workspace() from the filterbank held now
+        self._basis_key = key
+
+    @property
+    def _kmax(self):
+        """1 + the highest DFT bin that carries filter weight in the CURRENT mel_basis (0: none, the kernel keeps every bin)"""
+        self._sync_filterbank()
+        return self._kmax_value
+
+    def set_mel_basis(self, basis):
+        """replace the filterbank ([n_mel, n_fft/2 + 1] array or tensor, e.g. librosa.filters.mel); the same as mel_basis.copy_(...)"""
+        with torch.no_grad():
+            self.mel_basis.copy_(torch.as_tensor(np.asarray(basis) if not torch.is_tensor(basis) else basis))
+        self._sync_filterbank()
+
     def _workspace(self):
         from . import kernels as K
-        if self._fft_ws is None or self._fft_ws.device != self.mel_basis.device:
-            self._fft_ws = K.mel_prepare(self.mel_basis.contiguous(), self.n_fft)
+        self._sync_filterbank()
+        if self._fft_ws is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("TacotronSTFT (ctts_amd): call the module once before capturing a graph - its workspace is built by "
+                                   "a kernel launch, which a capture would only record")
+            self._fft_ws = K.mel_prepare(self.mel_basis.detach().float().contiguous(), self.n_fft)
         return self._fft_ws
 
     def mel_spectrogram(self, y):
-        """y [B,N] float32 on the HIP device, values in [-1, 1] (asserted like stft.py:177-178)."""
+        """y [B,N] float32 on the HIP device, values in [-1, 1] (asserted like stft.py:177-178, over the whole waveform: the FFT kernel
+        also reads, for the check alone, the samples that no frame loads when hop > n_fft/2 + 1)."""
         if not y.is_cuda:
             raise RuntimeError("TacotronSTFT (ctts_amd) computes on the MI355X: pass a device tensor")
         if self._dft_basis.device != y.device:
@@ -349,6 +394,7 @@ class TacotronSTFT(nn.Module):
             return mel, energy
         lo, hi = torch.aminmax(y.detach())              # DFT-as-GEMM path (other FFT sizes): one reduction + one sync for the two asserts
         assert lo >= -1 and hi <= 1
+        self._sync_filterbank()
         mel, energy, _ = ops.mel_spectrogram(y.float(), self._dft_basis, self._mel_basis_padded, self.n_fft, self.hop,
                                              self.n_mel_channels, self.nbins)
         return mel, energy
@@ -361,6 +407,7 @@ class TacotronSTFT(nn.Module):
             _, _, mag = K.mel_spectrogram_fft(y.float().contiguous(), self._window, self._workspace(), self.n_fft, self.hop,
                                               self.n_mel_channels, want_mag=True, kmax=self._kmax)
             return mag.view(y.shape[0], -1, mag.shape[-1])[:, :, :self.nbins].transpose(1, 2)
+        self._sync_filterbank()
         _, _, mag = ops.mel_spectrogram(y.float(), self._dft_basis, self._mel_basis_padded, self.n_fft, self.hop,
                                         self.n_mel_channels, self.nbins)
         B = y.shape[0]

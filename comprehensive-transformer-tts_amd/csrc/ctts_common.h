@@ -121,6 +121,12 @@ __device__ __forceinline__ float ctts_wave_max(float v) {
   return v;
 }
 
+// log(max(v, clip)) of the mel front end (csrc/mel.hip, csrc/elementwise.hip log_clamp_transpose).  The floor itself - every bin of a
+// silent frame - is the correctly rounded float32 log(clip), computed once on the host in double: the device logf is good to about
+// 2 ulp, which at log(1e-5) = -11.5 put the two paths' most frequent value two float32 steps off the reference's.
+inline float ctts_log_of_clip(float clip) { return (float)log((double)clip); }
+__device__ __forceinline__ float ctts_log_clamp(float v, float clip, float log_clip) { return v > clip ? logf(v) : log_clip; }
+
 // ---------------------------------------------------------------- bit-reproducible cross-workgroup reductions (round 4)
 // No floating-point atomics anywhere on the gradient path: the order in which workgroups reach an atomicAdd changes from run to run, so
 // two runs of the same train step from the same seed differed in the 7th digit and drifted apart (Adam amplifies: profiles/

@@ -225,10 +225,10 @@ __global__ __launch_bounds__(256) void stft_magnitude_kernel(const float* __rest
 
 // mel_fm [B*F, n_mel] -> out [B, n_mel, F] = log(max(v, clip))
 __global__ void log_clamp_transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int F, int n_mel,
-                                           float clip, long total) {
+                                           float clip, float log_clip, long total) {
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const int f = (int)(e % F); const long t = e / F; const int m = (int)(t % n_mel); const long b = t / n_mel;
-    out[e] = logf(fmaxf(in[(b * F + f) * n_mel + m], clip));
+    out[e] = ctts_log_clamp(in[(b * F + f) * n_mel + m], clip, log_clip);
   }
 }
 
@@ -407,7 +407,7 @@ extern "C" int ctts_log_clamp_transpose(const float* mel_fm, float* out, int B, 
   const long total = (long)B * F * n_mel;
   if (total == 0) return 0;
   hipLaunchKernelGGL(log_clamp_transpose_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, mel_fm, out, F, n_mel,
-                     clip, total);
+                     clip, ctts_log_of_clip(clip), total);
   CTTS_CHECK_LAUNCH("ctts_log_clamp_transpose");
   return 0;
 }

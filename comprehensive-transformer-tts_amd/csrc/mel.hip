@@ -62,7 +62,7 @@ __device__ __forceinline__ float sample_reflect(const float* __restrict__ yb, in
 __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ y, const int32_t* __restrict__ lens, const float* __restrict__ window,
                                                    const float* __restrict__ ws,
                                                    float* __restrict__ mel, float* __restrict__ energy, float* __restrict__ mag_out,
-                                                   long ld_mag, int B, int N, int F, int hop, int n_mel, float clip, int MS,
+                                                   long ld_mag, int B, int N, int F, int hop, int n_mel, float clip, float log_clip, int MS,
                                                    unsigned* __restrict__ range_flag) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // largest |sample| this thread loaded (v_max3_f32 with |.| modifiers: one instruction per pair; fmax drops NaNs, which instead turn the
@@ -182,6 +182,14 @@ __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ y, c
       if (lane == 0 && f < F) energy[(long)b * F + f] = sqrtf(e2);
       CTTS_WAVE_SYNC();                                   // this wave's scratch is reused by its next frame
     }
+    // samples no frame loads: with hop > n_fft/2 + 1 the stretch after the utterance's last frame, with hop > n_fft also the gaps between
+    // frames - the reference's range asserts cover the whole waveform.  One scalar branch per tile; nothing is read for smaller hops.
+    if (hop > NFFT / 2 + 1 && f0 < Fb) {
+      const int f_last = min(f0 + TILE_F, Fb) - 1;      // the tile's last frame of the utterance; f * hop <= Nb: no overflow
+      const int q0 = (hop > NFFT ? f0 : Fb - 1) * hop + NFFT / 2;
+      const int q1 = f_last == Fb - 1 ? Nb : (hop > NFFT ? (f_last + 1) * hop - NFFT / 2 : 0);
+      for (int q = q0 + tid; q < q1; q += 256) { const float t = yb[q]; amax = fmaxf(amax, fabsf(t)); saw_nan |= !(t == t); }
+    }
     __syncthreads();                                      // the magnitude tile is complete (the mel phase reads every wave's rows)
     // ------------------------------------------------------------------ mel phase: [16 frames x K] x [K x 16 filters] per MFMA tile
     const int n_tiles16 = (n_mel + 15) / 16;
@@ -191,7 +199,12 @@ __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ y, c
     // the workgroup's tile counter instead, so that over four tiles every SIMD gets every share.
     const int role = (wave + it) & 3;
     for (int nt = role; nt < n_tiles16; nt += 4) {
-      const int klo = kr[2 * nt], khi = kr[2 * nt + 1];  // multiples of 4
+      const int klo = kr[2 * nt];                        // multiples of 4
+      int khi = kr[2 * nt + 1];
+      // kmax contract: the tile's row holds bins < MS - 1 only.  A filter tile that reaches further (a kmax smaller than the filterbank the
+      // workspace was prepared from) is never summed over the next frame's row: its outputs are NaN and the flag is raised.
+      const bool short_tile = khi > MS - 1;
+      if (short_tile) khi = klo;
       floatx4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
       const int fr = lane & 15, kq = lane >> 4;
       // A[frame][k] from the magnitude tile (LDS), B[k][filter] from the transposed filterbank (global, L2-resident; fr doubles as the
@@ -228,7 +241,8 @@ __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ y, c
       for (int r = 0; r < 4; ++r) acc[r] += acc2[r];
       // D: col = lane & 15 (filter), row = (lane >> 4) * 4 + reg (frame)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) T[(nt * 16 + (lane & 15)) * 17 + (lane >> 4) * 4 + r] = logf(fmaxf(acc[r], clip));
+      for (int r = 0; r < 4; ++r)
+        T[(nt * 16 + (lane & 15)) * 17 + (lane >> 4) * 4 + r] = short_tile ? __builtin_nanf("") : ctts_log_clamp(acc[r], clip, log_clip);
     }
     __syncthreads();
     for (int e = tid; e < n_mel * TILE_F; e += 256) {
@@ -240,6 +254,13 @@ __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ y, c
   // out-of-range or NaN input.  No traffic at all for valid input; the flag may live in pinned host memory (plain store: any offending
   // value will do, the host only tests for non-zero)
   if (range_flag && (amax > 1.0f || saw_nan)) *reinterpret_cast<volatile unsigned*>(range_flag) = saw_nan ? 0x7FC00000u : __float_as_uint(amax);
+  // a broken kmax contract has a NaN pattern of its own (ctts.h CTTS_MEL_FLAG_KMAX), which no sample produces; where both happen in one
+  // launch either word may land last - the host raises on any non-zero word, and the short tiles' outputs are NaN regardless
+  if (range_flag && tid == 0) {
+    bool kmax_broken = false;
+    for (int nt = 0; nt < (n_mel + 15) / 16; ++nt) kmax_broken |= kr[2 * nt + 1] > MS - 1;
+    if (kmax_broken) *reinterpret_cast<volatile unsigned*>(range_flag) = 0x7FC0004Bu;
+  }
 }
 
 // workspace set-up (once per filterbank): twiddles in double precision, the transposed / zero-padded mel basis and, per tile of 16
@@ -316,7 +337,7 @@ extern "C" int ctts_mel_spectrogram(const float* y, const int32_t* lens, const f
   }
   const int grid = (int)(tiles < resident ? tiles : resident);
   hipLaunchKernelGGL(mel_kernel, dim3(grid), dim3(256), lds_bytes, (hipStream_t)stream, y, lens, window, workspace, mel, energy, mag, (long)ld_mag,
-                     B, N, F, hop, n_mel, clip, MS, range_flag);
+                     B, N, F, hop, n_mel, clip, ctts_log_of_clip(clip), MS, range_flag);
   CTTS_CHECK_LAUNCH("ctts_mel_spectrogram");
   return 0;
 }

@@ -489,7 +489,14 @@ int ctts_mel_spectrogram(const float* y, const int32_t* lens, const float* windo
  * single-utterance result; the remaining frames of the row are don't-care. */
 /* kmax: 1 + the highest DFT bin with a non-zero filter weight (372 for fmax 8 kHz at 22.05 kHz), or 0 = unknown (all 513 bins are kept
  * in the on-chip magnitude tile).  A smaller tile lets three workgroups share a CU instead of two; results do not depend on it as long as
- * no filter reaches beyond bin kmax-1. */
+ * no filter reaches beyond bin kmax-1.
+ * The contract cannot be broken silently: ctts_mel_prepare records, per tile of 16 filters, the bin range that carries weight, and the
+ * kernel bounds every tile's range by the row stride it was launched with.  A tile that reaches beyond kmax (a kmax that belongs to
+ * another filterbank than the workspace) is not summed: its outputs are NaN for every frame, and range_flag, where given, receives
+ * CTTS_MEL_FLAG_KMAX.  kmax = 0 is always safe.
+ * The range check covers every sample of the waveform (of lens[b] samples for a ragged row): samples that no frame loads, which exist for
+ * hop > n_fft/2 + 1, are read for the check alone. */
+#define CTTS_MEL_FLAG_KMAX 0x7FC0004Bu
 
 /* ---------------------------------------------------------------------------------------
  * Fused multi-head attention (csrc/attn.hip): exact-fp32 MFMA, flash-style - the [T,T] score / probability tensors never reach HBM in
