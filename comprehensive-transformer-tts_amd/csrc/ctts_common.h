@@ -121,6 +121,48 @@ __device__ __forceinline__ float ctts_wave_max(float v) {
   return v;
 }
 
+// Sums of doubles over a workgroup in a fixed order.  There are TWO orders, on purpose: outputs were defined with one or the other and
+// keep their bits, so a kernel stays with the form it has and the two are never merged.
+//   shuffle form (256 threads): the xor tree over each wave's lanes, then the four wave sums left to right
+//   tree form: halving tree over the workgroup's values in LDS (thread t adds t + h for h = THREADS / 2 ... 1)
+__device__ __forceinline__ double ctts_wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);         // every lane adds the same two values: one order
+  return v;
+}
+// red: 4 doubles of LDS; every thread gets the result.  The leading barrier lets `red` be reused by back-to-back calls.
+__device__ __forceinline__ double ctts_block_sum_d(double v, double* red, int tid) {
+  v = ctts_wave_sum_d(v);
+  __syncthreads();
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+// NV sums at once; red: NV * THREADS doubles of LDS; every thread gets the totals
+template <int NV, int THREADS>
+__device__ __forceinline__ void ctts_block_tree_sum(double (&v)[NV], double* red) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < NV; ++k) red[k * THREADS + tid] = v[k];
+  __syncthreads();
+  for (int h = THREADS / 2; h > 0; h >>= 1) {
+    if (tid < h) {
+#pragma unroll
+      for (int k = 0; k < NV; ++k) red[k * THREADS + tid] += red[k * THREADS + tid + h];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < NV; ++k) v[k] = red[k * THREADS];
+}
+template <int THREADS>
+__device__ __forceinline__ double ctts_block_tree_sum(double v, double* red) {
+  double a[1] = {v};
+  ctts_block_tree_sum<1, THREADS>(a, red);
+  return a[0];
+}
+
 // log(max(v, clip)) of the mel front end (csrc/mel.hip, csrc/elementwise.hip log_clamp_transpose).  The floor itself - every bin of a
 // silent frame - is the correctly rounded float32 log(clip), computed once on the host in double: the device logf is good to about
 // 2 ulp, which at log(1e-5) = -11.5 put the two paths' most frequent value two float32 steps off the reference's.

@@ -3,7 +3,7 @@
 //
 // The reference runs both directions as conv1d / conv_transpose1d against a dense [1026 x 1024] windowed basis (4.2 MFLOP per frame and
 // iteration).  Here each frame is one wave: a 1024-point real FFT = a 512-point complex FFT (z[m] = x[2m] + i x[2m+1], three radix-8
-// Stockham passes, 8 points per lane, exchange through the wave's own LDS scratch - the csrc/mel.hip scheme, its device functions copied)
+// Stockham passes, 8 points per lane, exchange through the wave's own LDS scratch - fft512 of fft_common.h, shared with csrc/mel.hip)
 // plus the even/odd split; the inverse runs the same forward FFT on the conjugated, re-merged half spectrum.  The inverse basis
 // pinv(scale F)^T window is exactly window * irfft / scale (F has full column rank; the pseudo-inverse projects out the imaginary parts
 // of bins 0 and 512, whose basis rows are zero, and inverts the rest), so no dense matrix exists anywhere.
@@ -27,107 +27,17 @@
 // pure function of those four, so an utterance's start does not depend on the batch around it, and no [B, 513, F] angle tensor exists.
 #include <float.h>
 #include "ctts_common.h"
+#include "fft_common.h"
 
 namespace {
 
 constexpr int NFFT = 1024, HOP = 256, NBINS = 513;
-constexpr int SCR = 584;                   // per-wave FFT scratch: 512 complex + padding (pad32)
-// workspace layout (floats): W512 (cos, sin) [1024] | W1024 k = 0..257 (cos, sin) [516] | window [1024] | window^2 [1024]
-constexpr int WS_W512 = 0, WS_W1024 = 1024, WS_WIN = 1540, WS_W2 = WS_WIN + NFFT, WS_FLOATS = WS_W2 + NFFT;
-// LDS: W512 | W1024 | the 7 x 8 twiddles of FFT pass 1 | window^2 | 4 waves x scratch
-constexpr int LDS_TW1 = 1540, LDS_W2 = 1540 + 112, LDS_SCR = LDS_W2 + NFFT, LDS_FLOATS = LDS_SCR + 4 * 2 * SCR;
+// workspace layout (floats): the FFT tables [1540] (fft_common.h) | window [1024] | window^2 [1024]
+constexpr int WS_WIN = FFT_TW_FLOATS, WS_W2 = WS_WIN + NFFT, WS_FLOATS = WS_W2 + NFFT;
+// LDS: the FFT tables and the pass-1 row (fft512_load_tables) | window^2 | 4 waves x scratch
+constexpr int LDS_TW1 = FFT_TW_FLOATS, LDS_W2 = FFT_TW_FLOATS + FFT_TW1_FLOATS, LDS_SCR = LDS_W2 + NFFT, LDS_FLOATS = LDS_SCR + 4 * 2 * SCR;
 constexpr int MAX_GRID = 1024;             // workgroups of a frame launch: 4 per CU of the 256, each wave walks its frames
 constexpr int STATE_SLOT = 4 * 256 + 4;    // floats of a frame's momentum state: float4 (X[k], X[512 - k]) [4][64] | X[256] | 2 floats of padding
-
-struct float2_ { float x, y; };
-__device__ __forceinline__ float2_ cmul(float2_ a, float2_ b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ void fft2(float2_& a, float2_& b) { const float2_ t = a; a = {t.x + b.x, t.y + b.y}; b = {t.x - b.x, t.y - b.y}; }
-__device__ __forceinline__ float2_ mul_mi(float2_ a) { return {a.y, -a.x}; }       // * (-i)
-__device__ __forceinline__ void fft4(float2_& v0, float2_& v1, float2_& v2, float2_& v3) {
-  fft2(v0, v2); fft2(v1, v3); v3 = mul_mi(v3); fft2(v0, v1); fft2(v2, v3);
-}
-// forward 8-point DFT in place; afterwards X[0..7] = v0, v4, v2, v6, v1, v5, v3, v7
-__device__ __forceinline__ void fft8(float2_ (&v)[8]) {
-  constexpr float h = 0.70710678118654752440f;
-  fft2(v[0], v[4]); fft2(v[1], v[5]); fft2(v[2], v[6]); fft2(v[3], v[7]);
-  v[5] = {(v[5].x + v[5].y) * h, (v[5].y - v[5].x) * h};
-  v[6] = mul_mi(v[6]);
-  v[7] = {(v[7].y - v[7].x) * h, -(v[7].x + v[7].y) * h};
-  fft4(v[0], v[1], v[2], v[3]); fft4(v[4], v[5], v[6], v[7]);
-}
-__device__ __forceinline__ int brev3(int r) { return ((r & 1) << 2) | (r & 2) | (r >> 2); }
-__device__ __forceinline__ int pad32(int i) { return i + (i >> 5) + ((i >> 6) << 3); }
-
-// the scratch S is private to a wave: program-ordered LDS accesses, no workgroup barrier (csrc/mel.hip)
-#define CTTS_WAVE_SYNC() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier()
-
-// 512-point forward complex FFT of v[r] = z[lane + 64 r]; leaves Z[k] at S[pad32(k)]
-__device__ __forceinline__ void fft512(float2_ (&v)[8], float* S, const float* tw512, const float* tw1, int lane) {
-  fft8(v);
-  CTTS_WAVE_SYNC();                                     // every earlier read of S by this wave is done
-#pragma unroll
-  for (int r = 0; r < 8; ++r) { const int o = pad32(lane * 8 + r); S[2 * o] = v[brev3(r)].x; S[2 * o + 1] = v[brev3(r)].y; }
-  CTTS_WAVE_SYNC();
-#pragma unroll
-  for (int pass = 1; pass < 3; ++pass) {
-    const int Ns = pass == 1 ? 8 : 64;
-    const int jm = lane & (Ns - 1);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) { const int o = pad32(lane + 64 * r); v[r] = {S[2 * o], S[2 * o + 1]}; }
-#pragma unroll
-    for (int r = 1; r < 8; ++r) {
-      const float* tw = pass == 1 ? tw1 + 2 * ((r - 1) * 8 + jm) : tw512 + 2 * (jm * r);
-      v[r] = cmul(v[r], float2_{tw[0], tw[1]});
-    }
-    fft8(v);
-    CTTS_WAVE_SYNC();
-    const int idx = (lane / Ns) * Ns * 8 + jm;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) { const int o = pad32(idx + r * Ns); S[2 * o] = v[brev3(r)].x; S[2 * o + 1] = v[brev3(r)].y; }
-    CTTS_WAVE_SYNC();
-  }
-}
-
-// even / odd split after fft512: bins k = lane + 64 m (m < 4), their mirrors 512 - k, and bin 256 (same value in every lane)
-__device__ __forceinline__ void split_bins(const float* S, const float* tw1024, int lane, float2_ (&xk)[4], float2_ (&xm)[4], float2_& x256) {
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int k = lane + 64 * m;
-    const int o1 = pad32(k), o2 = pad32((512 - k) & 511);
-    const float a = S[2 * o1], b = S[2 * o1 + 1], c = S[2 * o2], d = S[2 * o2 + 1];
-    const float er = 0.5f * (a + c), ei = 0.5f * (b - d), orr = 0.5f * (b + d), oi = -0.5f * (a - c);
-    const float wr = tw1024[2 * k], wi = tw1024[2 * k + 1];
-    const float tr = wr * orr - wi * oi, ti = wr * oi + wi * orr;
-    xk[m] = {er + tr, ei + ti};                         // X[k]       = E + W^k O
-    xm[m] = {er - tr, ti - ei};                         // X[512 - k] = conj(E - W^k O)
-  }
-  const int o = pad32(256);
-  x256 = {S[2 * o], -S[2 * o + 1]};                     // X[256] = conj(Z[256])
-}
-
-// inverse of split_bins: writes conj(Z') for the half spectrum X' (imaginary parts of bins 0 and 512 dropped) so that the forward FFT
-// of S gives 512 conj(z'), z'[m] = x[2m] + i x[2m+1] of x = irfft(X')
-__device__ __forceinline__ void merge_bins(float* S, const float* tw1024, int lane, const float2_ (&xk)[4], const float2_ (&xm)[4], float2_ x256) {
-  CTTS_WAVE_SYNC();                                     // every lane has read S (split_bins)
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int k = lane + 64 * m;
-    float2_ a = xk[m], c = xm[m];
-    if (k == 0) { a.y = 0.f; c.y = 0.f; }
-    const float er = 0.5f * (a.x + c.x), ei = 0.5f * (a.y - c.y);       // E = (X[k] + conj X[512-k]) / 2
-    const float dr = 0.5f * (a.x - c.x), di = 0.5f * (a.y + c.y);       // D = (X[k] - conj X[512-k]) / 2,  O = D conj(W^k)
-    const float wr = tw1024[2 * k], wi = tw1024[2 * k + 1];
-    const float orr = dr * wr + di * wi, oi = di * wr - dr * wi;
-    const int o1 = pad32(k);
-    S[2 * o1] = er - oi; S[2 * o1 + 1] = -(ei + orr);   // conj(Z[k]),       Z[k] = E + i O
-    if (k) {
-      const int o2 = pad32(512 - k);
-      S[2 * o2] = er + oi; S[2 * o2 + 1] = ei - orr;    // conj(Z[512 - k]), Z[512-k] = conj(E) + i conj(O)
-    }
-  }
-  if (lane == 0) { const int o = pad32(256); S[2 * o] = x256.x; S[2 * o + 1] = x256.y; }     // conj(Z[256]) = X[256]
-  CTTS_WAVE_SYNC();
-}
 
 // inverse FFT of the spectrum merge_bins left in S, windowed, / (512 * 4) -> one frame of Y (float2 per lane and r: coalesced)
 __device__ __forceinline__ void inverse_to_frame(float* S, const float* tw512, const float* tw1, const float (&win)[16], int lane,
@@ -146,15 +56,8 @@ __device__ __forceinline__ void inverse_to_frame(float* S, const float* tw512, c
 }
 
 __device__ __forceinline__ void load_tables(float* lds, const float* __restrict__ ws, int tid) {
-  for (int e = tid; e < 1540; e += 256) lds[e] = ws[e];
-  if (tid < 56) { const int t = (tid & 7) * 8 * ((tid >> 3) + 1); lds[LDS_TW1 + 2 * tid] = ws[2 * t]; lds[LDS_TW1 + 2 * tid + 1] = ws[2 * t + 1]; }
+  fft512_load_tables(lds, ws, tid);
   for (int e = tid; e < NFFT; e += 256) lds[LDS_W2 + e] = ws[WS_W2 + e];
-}
-
-__device__ __forceinline__ int reflect(int u, int L) {
-  if (u < 0) u = -u;
-  if (u >= L) u = 2 * (L - 1) - u;
-  return min(max(u, 0), L - 1);
 }
 
 // overlap-added, window-sum-normalised, scaled signal at PRE-CROP position t (t = output index + 512) of an utterance with F frames
@@ -208,7 +111,7 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, 
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
       const int p = f * HOP + 2 * (lane + 64 * r) - NFFT / 2;
-      v[r] = {xb[reflect(p, Nb)] * win[2 * r], xb[reflect(p + 1, Nb)] * win[2 * r + 1]};
+      v[r] = {xb[ctts_reflect_index(p, Nb)] * win[2 * r], xb[ctts_reflect_index(p + 1, Nb)] * win[2 * r + 1]};
     }
     fft512(v, S, lds + WS_W512, lds + LDS_TW1, lane);
     float2_ xk[4], xm[4], x256;
@@ -327,7 +230,7 @@ __global__ __launch_bounds__(256) void gl_iter_kernel(const float* __restrict__ 
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
         const int u = base + 2 * (lane + 64 * r);
-        v[r] = {ola_sample(Yb, w2, Fb, reflect(u, L) + NFFT / 2) * win[2 * r], ola_sample(Yb, w2, Fb, reflect(u + 1, L) + NFFT / 2) * win[2 * r + 1]};
+        v[r] = {ola_sample(Yb, w2, Fb, ctts_reflect_index(u, L) + NFFT / 2) * win[2 * r], ola_sample(Yb, w2, Fb, ctts_reflect_index(u + 1, L) + NFFT / 2) * win[2 * r + 1]};
       }
     }
     fft512(v, S, lds + WS_W512, lds + LDS_TW1, lane);
@@ -377,14 +280,7 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
 
 __global__ void gl_prepare_kernel(const float* __restrict__ window, float* __restrict__ ws) {
   const int tid = threadIdx.x;
-  for (int m = tid; m < 512; m += blockDim.x) {
-    double s, c; sincos(-2.0 * 3.14159265358979323846 * m / 512.0, &s, &c);
-    ws[WS_W512 + 2 * m] = (float)c; ws[WS_W512 + 2 * m + 1] = (float)s;
-  }
-  for (int m = tid; m < 258; m += blockDim.x) {
-    double s, c; sincos(-2.0 * 3.14159265358979323846 * m / 1024.0, &s, &c);
-    ws[WS_W1024 + 2 * m] = m <= 256 ? (float)c : 0.f; ws[WS_W1024 + 2 * m + 1] = m <= 256 ? (float)s : 0.f;
-  }
+  fft512_fill_tables(ws, tid, blockDim.x);
   for (int n = tid; n < NFFT; n += blockDim.x) { const float w = window[n]; ws[WS_WIN + n] = w; ws[WS_W2 + n] = w * w; }
 }
 

@@ -214,19 +214,6 @@ __global__ __launch_bounds__(256) void scan_kernel(const int32_t* __restrict__ l
   }
 }
 
-// sum of one double per thread in a fixed tree; every thread gets the result
-__device__ __forceinline__ double ld_block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int h = LD_GATE_THREADS / 2; h > 0; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 __global__ __launch_bounds__(LD_GATE_THREADS) void gate_kernel(const double* __restrict__ hop_sums, const int32_t* __restrict__ lens,
                                                                const int32_t* __restrict__ n_blocks, const int32_t* __restrict__ edges,
                                                                const int32_t* __restrict__ chunk_seg, const int32_t* __restrict__ blocks,
@@ -268,8 +255,8 @@ __global__ __launch_bounds__(LD_GATE_THREADS) void gate_kernel(const double* __r
       s += z[j];
       cnt += 1.0;
     }
-  s = ld_block_sum(s, red);
-  cnt = ld_block_sum(cnt, red);
+  s = ctts_block_tree_sum<LD_GATE_THREADS>(s, red);
+  cnt = ctts_block_tree_sum<LD_GATE_THREADS>(cnt, red);
   double L = -INFINITY;
   if (cnt > 0.0) {
     const double gr = -0.691 + 10.0 * log10(s / cnt) - 10.0;
@@ -282,8 +269,8 @@ __global__ __launch_bounds__(LD_GATE_THREADS) void gate_kernel(const double* __r
         cnt += 1.0;
       }
     }
-    s = ld_block_sum(s, red);
-    cnt = ld_block_sum(cnt, red);
+    s = ctts_block_tree_sum<LD_GATE_THREADS>(s, red);
+    cnt = ctts_block_tree_sum<LD_GATE_THREADS>(cnt, red);
     if (cnt > 0.0) L = -0.691 + 10.0 * log10(s / cnt);
   }
   if (tid == 0) {

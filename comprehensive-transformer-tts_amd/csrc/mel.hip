@@ -9,6 +9,7 @@
 // log-clamp fused, output transposed through LDS so that both mel [B,n_mel,F] rows and the input reads are coalesced.
 // HBM traffic = the algorithmic 1 KB in + 324 B out per frame (every sample is re-read by 4 overlapping frames from L1/L2).
 #include "ctts_common.h"
+#include "fft_common.h"
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
@@ -17,47 +18,14 @@ namespace {
 constexpr int NFFT = 1024, NC = 512, NBINS = 513;
 constexpr int TILE_F = 16;                 // frames per workgroup tile (4 waves x 4 frames)
 constexpr int MS_MAX = 517;                // magnitude-tile row stride when every bin may carry filter weight (odd: conflict-free column reads)
-constexpr int SCR = 584;                   // per-wave FFT scratch: 512 complex + padding (pad32: index + index/32 + 8 * (index/64))
-constexpr int LDS_HDR = 1540 + 112;        // twiddle tables in LDS: W512 | W1024 | the 7 x 8 twiddles of FFT pass 1, one row per r
-// workspace layout (floats): [0, 1024) W512 (cos, sin) | [1024, 1024+516) W1024 k = 0..256 (cos, sin) | melT [516][96] | int32 kranges[12]
-constexpr int WS_W512 = 0, WS_W1024 = 1024, WS_MELT = 1024 + 516, WS_KR = WS_MELT + 516 * 96, WS_FLOATS = WS_KR + 16;
-
-struct float2_ { float x, y; };
-__device__ __forceinline__ float2_ cmul(float2_ a, float2_ b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ void fft2(float2_& a, float2_& b) { const float2_ t = a; a = {t.x + b.x, t.y + b.y}; b = {t.x - b.x, t.y - b.y}; }
-__device__ __forceinline__ float2_ mul_mi(float2_ a) { return {a.y, -a.x}; }       // * (-i)
-__device__ __forceinline__ void fft4(float2_& v0, float2_& v1, float2_& v2, float2_& v3) {
-  fft2(v0, v2); fft2(v1, v3); v3 = mul_mi(v3); fft2(v0, v1); fft2(v2, v3);         // -> X0 = v0, X2 = v1, X1 = v2, X3 = v3
-}
-// forward 8-point DFT in place; afterwards X[0..7] = v0, v4, v2, v6, v1, v5, v3, v7
-__device__ __forceinline__ void fft8(float2_ (&v)[8]) {
-  constexpr float h = 0.70710678118654752440f;
-  fft2(v[0], v[4]); fft2(v[1], v[5]); fft2(v[2], v[6]); fft2(v[3], v[7]);
-  v[5] = {(v[5].x + v[5].y) * h, (v[5].y - v[5].x) * h};        // * W8^1 = (1 - i)/sqrt2
-  v[6] = mul_mi(v[6]);                                          // * W8^2 = -i
-  v[7] = {(v[7].y - v[7].x) * h, -(v[7].x + v[7].y) * h};       // * W8^3 = (-1 - i)/sqrt2
-  fft4(v[0], v[1], v[2], v[3]); fft4(v[4], v[5], v[6], v[7]);
-}
-__device__ __forceinline__ int brev3(int r) { return ((r & 1) << 2) | (r & 2) | (r >> 2); }
-// scratch slot of complex element i.  Every exchange pattern of the three passes must spread a 16-lane group over all 64 banks
-// (8-byte accesses): consecutive i (pass reads, pass-2 writes), i = 8 * lane + r (pass-0 writes: + i/32 shifts every 4th lane by a
-// bank pair) and i = 64 * (lane / 8) + (lane & 7) + 8 r (pass-1 writes: + 8 * (i/64) moves the second 8-lane run 20 banks away from
-// the first; with i + i/32 alone the two runs overlapped in 12 of 16 banks - 2-way conflicts on all 8 writes of every lane).
-__device__ __forceinline__ int pad32(int i) { return i + (i >> 5) + ((i >> 6) << 3); }
+constexpr int LDS_HDR = FFT_TW_FLOATS + FFT_TW1_FLOATS;      // twiddle tables in LDS (fft_common.h): W512 | W1024 | the pass-1 row
+// workspace layout (floats): the FFT tables [1540] (fft_common.h) | melT [516][96] | int32 kranges[12]
+constexpr int WS_MELT = FFT_TW_FLOATS, WS_KR = WS_MELT + 516 * 96, WS_FLOATS = WS_KR + 16;
 
 __device__ __forceinline__ float sample_reflect(const float* __restrict__ yb, int N, int p) {
-  // index into the reflect-padded waveform (F.pad(..., mode="reflect") by n_fft/2 on both sides, stft.py:66-71)
-  int q = p - NFFT / 2;
-  if (q < 0) q = -q;
-  if (q >= N) q = 2 * (N - 1) - q;
-  q = min(max(q, 0), N - 1);
-  return yb[q];
+  // the reflect-padded waveform (F.pad(..., mode="reflect") by n_fft/2 on both sides, stft.py:66-71)
+  return yb[ctts_reflect_index(p - NFFT / 2, N)];
 }
-
-// The FFT scratch S is private to a wave: its 64 lanes exchange data through LDS in program order (LDS operations of one wave complete in
-// order), so the passes need no workgroup barrier - only a fence that keeps hipcc from moving LDS accesses across the exchange points.
-// (Round 2 had __syncthreads() there: five workgroup barriers per frame that made the four independent FFTs of a workgroup march in step.)
-#define CTTS_WAVE_SYNC() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier()
 
 __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ y, const int32_t* __restrict__ lens, const float* __restrict__ window,
                                                    const float* __restrict__ ws,
@@ -69,16 +37,13 @@ __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ y, c
   // frame's energy into NaN and are caught there): raises *range_flag when the waveform leaves [-1, 1] or holds a NaN (the reference's asserts)
   float amax = 0.f;
   bool saw_nan = false;
-  float* tw512 = lds;                                   // 1024
-  float* tw1024 = lds + 1024;                           // 516
-  float* tw1 = lds + 1540;                              // 56 complex: W512^(8 * jm * r) at [(r - 1) * 8 + jm]
+  float* tw512 = lds + WS_W512;                         // 1024
+  float* tw1024 = lds + WS_W1024;                       // 516
+  float* tw1 = lds + FFT_TW_FLOATS;                     // 56 complex: the pass-1 row
   float* magt = lds + LDS_HDR;                          // TILE_F x MS
   float* scr = magt + TILE_F * MS;                      // 4 waves x SCR complex (re | im interleaved)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int e = tid; e < 1540; e += 256) lds[e] = ws[e];
-  // pass 1 needs only 8 distinct twiddles per r (jm = lane & 7); read from the W512 table they sit 64 r bytes apart - up to 8 lanes of
-  // a group on one bank.  A row of 8 consecutive entries per r is conflict-free.
-  if (tid < 56) { const int t = (tid & 7) * 8 * ((tid >> 3) + 1); tw1[2 * tid] = ws[2 * t]; tw1[2 * tid + 1] = ws[2 * t + 1]; }
+  fft512_load_tables(lds, ws, tid);
   // only bins < MS-1 are kept in the tile (the filterbank is zero above fmax); columns >= 513 are K padding of the MFMA and stay zero
   for (int e = tid; e < TILE_F * 4; e += 256) { const int c = NBINS + (e & 3); if (c < MS) magt[(e >> 2) * MS + c] = 0.f; }
   const int* kr = reinterpret_cast<const int*>(ws + WS_KR);
@@ -124,6 +89,11 @@ __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ y, c
           v[r] = {a * win[2 * r], c * win[2 * r + 1]};
         }
       }
+      // The three passes are fft512() of fft_common.h - the definition, to be changed there first - written out.  Called as a function
+      // the same text compiles to the same count of multiplies and fused multiply-adds, but hipcc then fuses the OTHER product of each
+      // twiddle multiplication (v_pk_mul / v_pk_fma with swapped operand selects) and two thirds of the magnitudes move by an ulp: the
+      // spectra of this kernel keep the rounding they have, Griffin-Lim's keep that of the function.  No fence is needed before the
+      // first write of S: the frame ends in one.
       // pass 0 (Ns = 1): no twiddles
       fft8(v);
 #pragma unroll
@@ -148,7 +118,8 @@ __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ y, c
         for (int r = 0; r < 8; ++r) { const int o = pad32(idx + r * Ns); S[2 * o] = v[brev3(r)].x; S[2 * o + 1] = v[brev3(r)].y; }
         CTTS_WAVE_SYNC();
       }
-      // even / odd split: X[k] = E + W1024^k O, X[512-k] = conj(E - W1024^k O); magnitudes, energy
+      // even / odd split: X[k] = E + W1024^k O, X[512-k] = conj(E - W1024^k O); magnitudes, energy.  The split is split_bins of
+      // fft_common.h, fused with the magnitudes: a bin's real and imaginary part never outlive its iteration
       float e2 = 0.f;
       float* mrow = magt + fl * MS;
       float* gmag = (mag_out && f < F) ? mag_out + ((long)b * F + f) * ld_mag : nullptr;
@@ -267,14 +238,7 @@ __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ y, c
 // filters, the range of DFT bins in which any of them is non-zero
 __global__ void mel_prepare_kernel(const float* __restrict__ mel_basis, int n_mel, int nbins, float* __restrict__ ws) {
   const int tid = threadIdx.x;
-  for (int m = tid; m < 512; m += blockDim.x) {
-    double s, c; sincos(-2.0 * 3.14159265358979323846 * m / 512.0, &s, &c);
-    ws[WS_W512 + 2 * m] = (float)c; ws[WS_W512 + 2 * m + 1] = (float)s;
-  }
-  for (int m = tid; m < 258; m += blockDim.x) {
-    double s, c; sincos(-2.0 * 3.14159265358979323846 * m / 1024.0, &s, &c);
-    ws[WS_W1024 + 2 * m] = m <= 256 ? (float)c : 0.f; ws[WS_W1024 + 2 * m + 1] = m <= 256 ? (float)s : 0.f;
-  }
+  fft512_fill_tables(ws, tid, blockDim.x);
   for (int e = tid; e < 516 * 96; e += blockDim.x) {
     const int k = e / 96, n = e - k * 96;
     ws[WS_MELT + e] = (k < nbins && n < n_mel) ? mel_basis[(long)n * nbins + k] : 0.f;

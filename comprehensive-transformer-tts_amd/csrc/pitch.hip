@@ -9,18 +9,7 @@
 
 namespace {
 
-constexpr int PITCH_THREADS = 256;
-
-__device__ __forceinline__ double pitch_block_sum(double v, double* s_red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < PITCH_THREADS / 64; ++w) t += s_red[w];
-  return t;
-}
+constexpr int PITCH_THREADS = 256;              // ctts_block_sum_d is written for 256
 
 __global__ __launch_bounds__(PITCH_THREADS) void cwt_pitch_kernel(const float* __restrict__ spec, long ld_spec, int nscale, const float* __restrict__ f0_mean,
                                                                     const float* __restrict__ f0_std, float std_scale, const float* __restrict__ uv,
@@ -40,10 +29,10 @@ __global__ __launch_bounds__(PITCH_THREADS) void cwt_pitch_kernel(const float* _
     s_rec[t] = r;
     sum += (double)r;
   }
-  const double mean = pitch_block_sum(sum, s_red) / (double)T;
+  const double mean = ctts_block_sum_d(sum, s_red, threadIdx.x) / (double)T;
   double sq = 0.0;
   for (int t = threadIdx.x; t < T; t += PITCH_THREADS) { const double dlt = (double)s_rec[t] - mean; sq += dlt * dlt; }
-  const double var = pitch_block_sum(sq, s_red) / (double)(T - 1);            // unbiased (torch.std default); T = 1: 0 / 0 = NaN like torch
+  const double var = ctts_block_sum_d(sq, s_red, threadIdx.x) / (double)(T - 1);            // unbiased (torch.std default); T = 1: 0 / 0 = NaN like torch
   const float meanf = (float)mean, stdf = (float)sqrt(var);
   const float m = f0_mean[b], sd = f0_std[b] * std_scale;
   const float mel_span = mel_max - mel_min;

@@ -3,7 +3,7 @@
 //
 // pitch_track_kernel - one wave per frame, four frames per wave, 16 per workgroup.  A frame's 1024 windowed samples go through a 2048-point
 //   zero-padded real FFT = one 1024-point complex FFT (z[n] = x[2n] + i x[2n+1], five radix-4 Stockham passes, 16 points per lane, exchange
-//   through the wave's own LDS scratch, no workgroup barrier: see CTTS_WAVE_SYNC in mel.hip) + the even/odd split; the power spectrum is
+//   through the wave's own LDS scratch, no workgroup barrier: see CTTS_WAVE_SYNC in fft_common.h) + the even/odd split; the power spectrum is
 //   real and even, so the way back is the SAME transform (its real part is 2048 r(tau)).  Normalisation by the window's autocorrelation,
 //   the candidate search and the octave-cost argmax stay in LDS and registers: HBM traffic = the samples in, 8 bytes per frame out.
 // f0_targets_kernel - one workgroup per utterance: nearest voiced neighbour on both sides (chunked scan), continuous log-F0, mean / std in
@@ -11,6 +11,7 @@
 //   wavelet's spectrum is real, so two scales ride in the real and imaginary part of one inverse transform), all in LDS.
 // No float atomics, no inter-workgroup waits, every loop statically bounded: results are bit-reproducible and batch-independent.
 #include "ctts_common.h"
+#include "fft_common.h"
 #include <math.h>
 
 namespace {
@@ -22,13 +23,6 @@ constexpr int PW = 1028;                                     // per-wave power s
 constexpr int FRAMES_PER_WAVE = 4, FRAMES_PER_WG = 16;
 constexpr int PEAK_SLICES = 32;                             // the utterance peak is reduced in 32 slices per utterance
 
-struct cf { float x, y; };
-__device__ __forceinline__ cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ cf cadd(cf a, cf b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ cf csub(cf a, cf b) { return {a.x - b.x, a.y - b.y}; }
-
-#define PT_WAVE_SYNC() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier()
-
 // In-place forward 1024-point complex FFT of the wave's scratch S (natural order in and out): Stockham radix 4, butterfly j = lane + 64 q
 // reads S[j + 256 r], multiplies by W1024^(r k 256 / Ns) (k = j mod Ns) and writes S[4 (j - k) + k + r Ns].  Every lane holds all 16 of its
 // inputs before any lane writes (the wave runs in lockstep between the two fences), which is what makes the in-place update safe.
@@ -36,7 +30,7 @@ __device__ __forceinline__ void fft1024(float* __restrict__ S, const float* __re
 #pragma unroll
   for (int pass = 0; pass < 5; ++pass) {
     const int Ns = 1 << (2 * pass);
-    cf u[4][4];
+    float2_ u[4][4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int j = lane + 64 * q;
@@ -49,29 +43,29 @@ __device__ __forceinline__ void fft1024(float* __restrict__ S, const float* __re
       if (pass > 0) {
         const int m = k * (256 / Ns);
 #pragma unroll
-        for (int r = 1; r < 4; ++r) u[q][r] = cmul(u[q][r], cf{tw[2 * (r * m)], tw[2 * (r * m) + 1]});
+        for (int r = 1; r < 4; ++r) u[q][r] = cmul(u[q][r], float2_{tw[2 * (r * m)], tw[2 * (r * m) + 1]});
       }
-      const cf t0 = cadd(u[q][0], u[q][2]), t1 = csub(u[q][0], u[q][2]), t2 = cadd(u[q][1], u[q][3]), d = csub(u[q][1], u[q][3]);
-      const cf t3 = {d.y, -d.x};                                  // * (-i)
+      const float2_ t0 = cadd(u[q][0], u[q][2]), t1 = csub(u[q][0], u[q][2]), t2 = cadd(u[q][1], u[q][3]), d = csub(u[q][1], u[q][3]);
+      const float2_ t3 = {d.y, -d.x};                                  // * (-i)
       u[q][0] = cadd(t0, t2); u[q][1] = cadd(t1, t3); u[q][2] = csub(t0, t2); u[q][3] = csub(t1, t3);
     }
-    PT_WAVE_SYNC();
+    CTTS_WAVE_SYNC();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int j = lane + 64 * q, k = j & (Ns - 1), j0 = ((j - k) << 2) + k;
 #pragma unroll
       for (int r = 0; r < 4; ++r) { S[2 * (j0 + r * Ns)] = u[q][r].x; S[2 * (j0 + r * Ns) + 1] = u[q][r].y; }
     }
-    PT_WAVE_SYNC();
+    CTTS_WAVE_SYNC();
   }
 }
 
 // bins k and 1024 - k of the 2048-point transform of the real sequence packed into S: X[k] = E + W2048^k O, X[1024 - k] = conj(E - W2048^k O)
-__device__ __forceinline__ void split_pair(const float* __restrict__ S, const float* __restrict__ tw2, int k, cf& xa, cf& xb) {
+__device__ __forceinline__ void split_pair(const float* __restrict__ S, const float* __restrict__ tw2, int k, float2_& xa, float2_& xb) {
   const int km = (NZ - k) & (NZ - 1);
   const float a = S[2 * k], b = S[2 * k + 1], c = S[2 * km], d = S[2 * km + 1];
-  const cf E = {0.5f * (a + c), 0.5f * (b - d)}, O = {0.5f * (b + d), -0.5f * (a - c)};
-  const cf t = cmul(cf{tw2[2 * k], tw2[2 * k + 1]}, O);
+  const float2_ E = {0.5f * (a + c), 0.5f * (b - d)}, O = {0.5f * (b + d), -0.5f * (a - c)};
+  const float2_ t = cmul(float2_{tw2[2 * k], tw2[2 * k + 1]}, O);
   xa = cadd(E, t);
   xb = csub(E, t);                                                // conjugate not taken: only |.|^2 or the real part is used
 }
@@ -140,36 +134,36 @@ __global__ __launch_bounds__(256) void pitch_track_kernel(const float* __restric
         S[2 * n] = (xs[2 * m] - mean) * win[2 * m]; S[2 * n + 1] = (xs[2 * m + 1] - mean) * win[2 * m + 1];
         S[2 * (n + 512)] = 0.f; S[2 * (n + 512) + 1] = 0.f;      // the zero padding to 2048 samples
       }
-      PT_WAVE_SYNC();
+      CTTS_WAVE_SYNC();
       fft1024(S, tw, lane);
       // ---- power spectrum P[0..1024] (P[2048 - k] = P[k])
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
         const int k = lane + 64 * m;
-        cf xa, xb; split_pair(S, tw2, k, xa, xb);
+        float2_ xa, xb; split_pair(S, tw2, k, xa, xb);
         P[k] = xa.x * xa.x + xa.y * xa.y;
         P[NZ - k] = xb.x * xb.x + xb.y * xb.y;
       }
       if (lane == 0) { const float a = S[2 * 512], c = S[2 * 512 + 1]; P[512] = a * a + c * c; }    // E, O real and W2048^512 = -i: |X[512]| = |Z[512]|
-      PT_WAVE_SYNC();
+      CTTS_WAVE_SYNC();
       // ---- back: p[n] = P[n] (n <= 1024) or P[2048 - n], packed z[m] = p[2m] + i p[2m + 1]
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int m = lane + 64 * q, n0 = 2 * m, n1 = 2 * m + 1;
         S[2 * m] = P[n0 <= 1024 ? n0 : 2048 - n0]; S[2 * m + 1] = P[n1 <= 1024 ? n1 : 2048 - n1];
       }
-      PT_WAVE_SYNC();
+      CTTS_WAVE_SYNC();
       fft1024(S, tw, lane);
       float r[8];
 #pragma unroll
-      for (int m = 0; m < 8; ++m) { cf xa, xb; split_pair(S, tw2, lane + 64 * m, xa, xb); r[m] = xa.x; }   // 2048 r(tau), tau = lane + 64 m
-      PT_WAVE_SYNC();
+      for (int m = 0; m < 8; ++m) { float2_ xa, xb; split_pair(S, tw2, lane + 64 * m, xa, xb); r[m] = xa.x; }   // 2048 r(tau), tau = lane + 64 m
+      CTTS_WAVE_SYNC();
       const float r0 = __shfl(r[0], 0, 64);
       if (r0 > 0.f && r0 < INFINITY) {
         float* rn = S;                                   // rn[tau], tau < 512
 #pragma unroll
         for (int m = 0; m < 8; ++m) { r[m] = (r[m] / r0) / rwn[lane + 64 * m]; rn[lane + 64 * m] = r[m]; }
-        PT_WAVE_SYNC();
+        CTTS_WAVE_SYNC();
         float best_cost = -INFINITY, best_lag = 0.f, best_h = 0.f;
         int best_tau = 0x7fffffff;
 #pragma unroll
@@ -198,7 +192,7 @@ __global__ __launch_bounds__(256) void pitch_track_kernel(const float* __restric
           if (best_h >= vthr && amax >= sthr * upeak) f0v = sr / best_lag;
         }
       }
-      PT_WAVE_SYNC();                                    // the scratch is reused by the wave's next frame
+      CTTS_WAVE_SYNC();                                    // the scratch is reused by the wave's next frame
     }
     if (lane == 0) { f0_out[g] = f0v; st_out[g] = stv; }
   }
@@ -233,15 +227,6 @@ constexpr int TMAX = 4096, NSCALE = 10;
 // dynamic LDS (floats): val [TMAX] | bufA, bufB, bufX [2 TMAX] each | twiddles [TMAX] (M / 2 complex) | int chunk summaries [512]
 constexpr int L_VAL = 0, L_A = TMAX, L_B = 3 * TMAX, L_X = 5 * TMAX, L_TW = 7 * TMAX, L_CH = 8 * TMAX, L_FLOATS = 8 * TMAX + 512;
 
-__device__ __forceinline__ double block_sum_d(double v, double* red, int tid) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // Stockham radix-2 FFT of M = 2^logM points by the whole workgroup, ping-pong between `in` and `out`; returns where the result lies
 __device__ __forceinline__ float* block_fft(float* in, float* out, const float* __restrict__ tw, int M, int logM, bool inverse, int tid) {
   const int half = M >> 1;
@@ -249,10 +234,10 @@ __device__ __forceinline__ float* block_fft(float* in, float* out, const float* 
     const int Ns = 1 << s;
     for (int j = tid; j < half; j += 256) {
       const int k = j & (Ns - 1), ti = k * (half >> s);
-      const cf a = {in[2 * j], in[2 * j + 1]};
-      cf w = {tw[2 * ti], tw[2 * ti + 1]};
+      const float2_ a = {in[2 * j], in[2 * j + 1]};
+      float2_ w = {tw[2 * ti], tw[2 * ti + 1]};
       if (inverse) w.y = -w.y;
-      const cf bb = cmul(cf{in[2 * (j + half)], in[2 * (j + half) + 1]}, w);
+      const float2_ bb = cmul(float2_{in[2 * (j + half)], in[2 * (j + half) + 1]}, w);
       const int j0 = ((j - k) << 1) + k;
       out[2 * j0] = a.x + bb.x; out[2 * j0 + 1] = a.y + bb.y;
       out[2 * (j0 + Ns)] = a.x - bb.x; out[2 * (j0 + Ns) + 1] = a.y - bb.y;
@@ -354,11 +339,11 @@ __global__ __launch_bounds__(256) void f0_targets_kernel(const float* __restrict
       bad |= !(fabsf(lf[i]) < INFINITY);
     }
   }
-  const double mean = block_sum_d(s1, red, tid) / (double)max(n, 1);
+  const double mean = ctts_block_sum_d(s1, red, tid) / (double)max(n, 1);
   double s2 = 0.0;
 #pragma unroll
   for (int i = 0; i < TMAX / 256; ++i) { const int t = tid + 256 * i; if (t < n) { const double d = (double)lf[i] - mean; s2 += d * d; } }
-  const double var = block_sum_d(s2, red, tid) / (double)max(n, 1);
+  const double var = ctts_block_sum_d(s2, red, tid) / (double)max(n, 1);
   // ---- validity, decided without leaving the device: no voiced frame, a constant track (std == 0 exactly when max == min) or a
   // non-finite value (f0 < 0, Inf, NaN) give valid = 0 and all-zero rows
 #pragma unroll

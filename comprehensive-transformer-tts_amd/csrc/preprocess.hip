@@ -10,27 +10,13 @@
 //   sort of its values in LDS, numpy's linear percentiles, the keep mask, then count / sum / M2 in double and min / max over the kept values.
 // No float atomics, no inter-workgroup waits, every reduction in a fixed order: results are bit-reproducible and batch-independent.
 #include "ctts_common.h"
+#include "fft_common.h"
 #include <math.h>
 
 namespace {
 
 constexpr int TRIM_FRAMES_PER_WG = 4;                  // one wave per frame
 constexpr int OUT_MAX = 4096;                          // values per utterance the outlier kernel sorts in LDS
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// sum over the workgroup's 256 threads in a fixed order (lane tree, then the four waves left to right); every thread gets the result
-__device__ __forceinline__ double block_sum_d(double v, double* red, int tid) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // ------------------------------------------------------------------------------------------------------------------ silence trim
 // mse[b][f] = mean of squares of frame f of utterance b: padded samples [f hop, f hop + frame_length), padded sample p = x[reflect(p -
@@ -47,14 +33,11 @@ __global__ __launch_bounds__(256) void frame_power_kernel(const float* __restric
     const long base = (long)f * hop - frame_length / 2;
     double acc = 0.0;
     for (int k = lane; k < frame_length; k += 64) {
-      long i = base + k;
-      if (i < 0) i = -i;
-      if (i >= len) i = 2L * (len - 1) - i;
-      i = min(max(i, 0L), (long)len - 1);                 // only reached when len <= frame_length / 2 (outside the domain): stay in bounds
+      const long i = ctts_reflect_index(base + k, (long)len);     // its clamp acts only when len <= frame_length / 2 (outside the domain)
       const double v = (double)x[i];
       acc += v * v;
     }
-    out = (float)(wave_sum_d(acc) / (double)frame_length);
+    out = (float)(ctts_wave_sum_d(acc) / (double)frame_length);
   }
   if (lane == 0) mse[(long)b * F + f] = out;
 }
@@ -178,7 +161,7 @@ __global__ __launch_bounds__(256) void outlier_stats_kernel(const float* __restr
     hi = fmaxf(hi, __shfl_xor(hi, o, 64));
   }
   if ((tid & 63) == 0) { redi[tid >> 6] = cnt; redf[tid >> 6] = lo; redf[4 + (tid >> 6)] = hi; }
-  const double total = block_sum_d(s1, red, tid);        // its barriers also publish redi / redf
+  const double total = ctts_block_sum_d(s1, red, tid);        // its barriers also publish redi / redf
   cnt = redi[0] + redi[1] + redi[2] + redi[3];
   const double mean = cnt > 0 ? total / (double)cnt : 0.0;
   double s2 = 0.0;
@@ -186,7 +169,7 @@ __global__ __launch_bounds__(256) void outlier_stats_kernel(const float* __restr
     const double x = (double)v[i];
     if (x > lower && x < upper) { const double d = x - mean; s2 += d * d; }
   }
-  const double ss = block_sum_d(s2, red, tid);
+  const double ss = ctts_block_sum_d(s2, red, tid);
   if (tid == 0) {
     count[b] = cnt; sum[b] = total; m2[b] = ss;
     vmin[b] = fminf(fminf(redf[0], redf[1]), fminf(redf[2], redf[3]));

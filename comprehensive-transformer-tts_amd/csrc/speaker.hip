@@ -5,7 +5,7 @@
 //   span_kernel        one workgroup per utterance: the two order statistics of |x| around the 95th percentile by a four-pass radix
 //                      select on the bit patterns (non-negative floats order as their bits), the threshold in double, then the lowest and
 //                      highest sample above it.  Integer LDS atomics only: the result does not depend on the order of arrival.
-//   fbank_kernel       one workgroup per (output frame, utterance): pre-emphasis, a 1024-point FFT in LDS, the 64 triangular filters and the
+//   fbank_kernel       one workgroup per (output frame, utterance): pre-emphasis, a 1024-point FFT in LDS (fft_common.h), the 64 triangular filters and the
 //                      per-frame normalisation, all in DOUBLE (2560 frames per batch of 16: the fp64 rate is no concern and the features
 //                      leave with one fp32 rounding).
 //   conv_mfma_kernel   the implicit GEMM  out[m][n] = sum_k A[m][k] W[k][n],  m = (b, oh, ow), k = (kh, kw, cin), n = cout, on the exact
@@ -17,6 +17,7 @@
 //   head_kernel        mean over time, affine layer, L2 normalisation; one workgroup per utterance, sums in double in index order.
 // Every sum has a fixed order: results are bit-identical run to run and a row does not depend on the other rows.
 #include "ctts_common.h"
+#include "fft_common.h"
 #include <math.h>
 
 namespace {
@@ -149,26 +150,11 @@ __global__ __launch_bounds__(SP_FB_THREADS) void fbank_kernel(const float* __res
       v = (double)x[pos];
       if (pos > 0) v -= SP_PREEMPH * (double)x[pos - 1];
     }
-    a[__brev((unsigned)i) >> 22] = make_double2(v, 0.0);
+    a[ctts_dfft_slot<SP_NFFT>(i)] = make_double2(v, 0.0);
   }
-  for (int i = tid; i < SP_NFFT / 2; i += SP_FB_THREADS) {
-    double s, c;
-    sincospi(-(double)i / (double)(SP_NFFT / 2), &s, &c);
-    tw[i] = make_double2(c, s);
-  }
+  ctts_dfft_fill_twiddles<SP_NFFT, SP_FB_THREADS>(tw, tid);
   __syncthreads();
-  for (int st = 1; st <= 10; ++st) {
-    const int half = 1 << (st - 1);
-    for (int t = tid; t < SP_NFFT / 2; t += SP_FB_THREADS) {
-      const int pos = t & (half - 1);
-      const int i0 = ((t >> (st - 1)) << st) + pos, i1 = i0 + half;
-      const double2 w = tw[pos << (10 - st)], u = a[i0], q = a[i1];
-      const double2 v = make_double2(q.x * w.x - q.y * w.y, q.x * w.y + q.y * w.x);
-      a[i0] = make_double2(u.x + v.x, u.y + v.y);
-      a[i1] = make_double2(u.x - v.x, u.y - v.y);
-    }
-    __syncthreads();
-  }
+  for (int s = 0; s < ctts_log2<SP_NFFT>::value; ++s) ctts_dfft_pass<SP_NFFT, SP_FB_THREADS>(a, tw, s, tid);
   for (int i = tid; i < SP_BINS; i += SP_FB_THREADS) P[i] = (a[i].x * a[i].x + a[i].y * a[i].y) / (double)SP_NFFT;
   __syncthreads();
   if (tid < SP_NFILT) {

@@ -6,7 +6,7 @@
 // STOI frames) and the MI355X runs fp64 vector arithmetic at half its fp32 rate, so the kernels sit three orders of magnitude under
 // the float32 evaluation of the same chain instead of beside it, and the keep decision of the silent-frame step is the restatement's.
 //   frame_spectrum<NFFT, EPI>  one workgroup per frame pair: both signals are windowed, packed as x + i y into ONE complex FFT of NFFT points
-//                          in LDS (radix 2, decimation in time) and unpacked by the Hermitian symmetry (in double the cross-talk of the
+//                          in LDS (radix 2, decimation in time: fft_common.h) and unpacked by the Hermitian symmetry (in double the cross-talk of the
 //                          packing is 2^-53 of the larger spectrum).  EPI_STOI gathers the frame through the kept-index list - the
 //                          compacted signals never exist - and writes the 15 third-octave band amplitudes of both signals; EPI_MR takes
 //                          frame i at i hop and writes the frame's four partial sums of the Parallel-WaveGAN distances.
@@ -18,6 +18,7 @@
 // No floating-point atomics, no workgroup waits on another; every sum is taken in an order fixed by the utterance's own indices, so a
 // row's result depends on nothing but the row.  Nothing at or beyond lens[b] is read.
 #include "ctts_common.h"
+#include "fft_common.h"
 #include <math.h>
 #include <algorithm>
 
@@ -37,25 +38,6 @@ __constant__ int ST_EDGE[ST_BANDS + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 
 
 __host__ __device__ __forceinline__ int wm_frames(int len, int win, int hop) { return len >= win ? (len - win) / hop + 1 : 0; }
 
-// sum of NV doubles per thread in a fixed tree over the workgroup; thread 0 holds the totals
-template <int NV>
-__device__ __forceinline__ void wm_block_sum(double (&v)[NV], double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) red[k * WM_THREADS + tid] = v[k];
-  __syncthreads();
-  for (int h = WM_THREADS / 2; h > 0; h >>= 1) {
-    if (tid < h) {
-#pragma unroll
-      for (int k = 0; k < NV; ++k) red[k * WM_THREADS + tid] += red[k * WM_THREADS + tid + h];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = red[k * WM_THREADS];
-}
-
 // ---------------------------------------------------------------- STOI: silent-frame step
 __global__ __launch_bounds__(WM_THREADS) void st_energy_kernel(const float* __restrict__ ref, const int32_t* __restrict__ lens,
                                                                const double* __restrict__ w, double* __restrict__ energy, int N, int Fa) {
@@ -70,8 +52,7 @@ __global__ __launch_bounds__(WM_THREADS) void st_energy_kernel(const float* __re
     const double p = w[lane + 64 * q] * (double)x[lane + 64 * q];
     s = fma(p, p, s);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);       // every lane adds the same two values: one order
+  s = ctts_wave_sum_d(s);
   if (lane == 0) energy[(long)b * Fa + i] = s;
 }
 
@@ -120,15 +101,6 @@ __global__ __launch_bounds__(WM_THREADS) void st_keep_kernel(const double* __res
 }
 
 // ---------------------------------------------------------------- the shared frame-spectrum kernel
-template <int NFFT>
-struct wm_log2 {
-  static constexpr int value = 1 + wm_log2<NFFT / 2>::value;
-};
-template <>
-struct wm_log2<1> {
-  static constexpr int value = 0;
-};
-
 // EPI_STOI: idx / counts drive the gather and `out` receives the band amplitudes [B][2][15][Fa];  EPI_MR: plain framing at fr * hop (idx and
 // counts are NULL) and `out` receives the frame partials [B][Fa][4].  Fa is the frame stride of the workspace rows.
 template <int NFFT, int EPI>
@@ -136,7 +108,6 @@ __global__ __launch_bounds__(WM_THREADS) void frame_spectrum(const float* __rest
                                                              const int32_t* __restrict__ lens, const double* __restrict__ w,
                                                              const int32_t* __restrict__ idx, const int32_t* __restrict__ counts,
                                                              double* __restrict__ out, int N, int Fa, int hop, int win) {
-  constexpr int LOG = wm_log2<NFFT>::value;
   __shared__ double2 a[NFFT];
   __shared__ double2 tw[NFFT / 2];
   __shared__ double red[EPI == EPI_MR ? 4 * WM_THREADS : 1];
@@ -151,11 +122,7 @@ __global__ __launch_bounds__(WM_THREADS) void frame_spectrum(const float* __rest
   } else {
     if (fr >= wm_frames(len, win, hop)) return;
   }
-  for (int k = tid; k < NFFT / 2; k += WM_THREADS) {
-    double s, c;
-    sincospi(-2.0 * (double)k / (double)NFFT, &s, &c);
-    tw[k] = make_double2(c, s);
-  }
+  ctts_dfft_fill_twiddles<NFFT, WM_THREADS>(tw, tid);
   for (int n = tid; n < NFFT; n += WM_THREADS) {
     double vx = 0.0, vy = 0.0;
     if (EPI == EPI_STOI) {
@@ -182,23 +149,11 @@ __global__ __launch_bounds__(WM_THREADS) void frame_spectrum(const float* __rest
       vx = w[n] * (double)x[p0];
       vy = w[n] * (double)y[p0];
     }
-    a[__brev((unsigned)n) >> (32 - LOG)] = make_double2(vx, vy);
+    a[ctts_dfft_slot<NFFT>(n)] = make_double2(vx, vy);
   }
   __syncthreads();
 #pragma unroll 1
-  for (int s = 0; s < LOG; ++s) {
-    const int half = 1 << s;
-    for (int t = tid; t < NFFT / 2; t += WM_THREADS) {
-      const int pos = t & (half - 1);
-      const int i = ((t >> s) << (s + 1)) + pos, j = i + half;
-      const double2 wv = tw[pos << (LOG - 1 - s)];
-      const double2 u = a[i], v = a[j];
-      const double vr = v.x * wv.x - v.y * wv.y, vi = v.x * wv.y + v.y * wv.x;
-      a[i] = make_double2(u.x + vr, u.y + vi);
-      a[j] = make_double2(u.x - vr, u.y - vi);
-    }
-    __syncthreads();
-  }
+  for (int s = 0; s < ctts_log2<NFFT>::value; ++s) ctts_dfft_pass<NFFT, WM_THREADS>(a, tw, s, tid);
   // Z = X + i Y with X, Y Hermitian:  |X_k|^2 = ((a + c)^2 + (b - d)^2) / 4,  |Y_k|^2 = ((b + d)^2 + (a - c)^2) / 4,  Z_k = a + i b, Z_{N-k} = c + i d
   auto power = [&](int k, double& px, double& py) {
     const double2 zk = a[k], zn = a[(NFFT - k) & (NFFT - 1)];
@@ -230,7 +185,7 @@ __global__ __launch_bounds__(WM_THREADS) void frame_spectrum(const float* __rest
       v[2] += fabs(l);
       v[3] = fma(l, l, v[3]);
     }
-    wm_block_sum<4>(v, red);
+    ctts_block_tree_sum<4, WM_THREADS>(v, red);
     if (tid == 0) {
       double* p = out + ((long)b * Fa + fr) * 4;
       p[0] = v[0];
@@ -254,7 +209,7 @@ __global__ __launch_bounds__(WM_THREADS) void mr_finish_kernel(const double* __r
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] += p[k];
   }
-  wm_block_sum<4>(v, red);
+  ctts_block_tree_sum<4, WM_THREADS>(v, red);
   if (tid == 0) {
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     out[b * 3 + 0] = nf > 0 ? sqrt(v[0] / v[1]) : nan;
@@ -352,7 +307,7 @@ __global__ __launch_bounds__(WM_THREADS) void st_finish_kernel(const double* __r
     v[0] += segv[((long)b * Fa + s) * 2 + 0];
     v[1] += segv[((long)b * Fa + s) * 2 + 1];
   }
-  wm_block_sum<2>(v, red);
+  ctts_block_tree_sum<2, WM_THREADS>(v, red);
   if (tid == 0) {
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     stoi[b] = S > 0 ? v[0] / ((double)ST_BANDS * (double)S) : nan;
@@ -393,7 +348,7 @@ __global__ __launch_bounds__(WM_THREADS) void sd_partial_kernel(const float* __r
       v[4] = fma(yd, yd, v[4]);
     }
   }
-  wm_block_sum<5>(v, red);
+  ctts_block_tree_sum<5, WM_THREADS>(v, red);
   if (tid == 0) {
     double* p = part + ((long)b * nt + tile) * 5;
 #pragma unroll
@@ -413,7 +368,7 @@ __global__ __launch_bounds__(WM_THREADS) void sd_finish_kernel(const double* __r
 #pragma unroll
     for (int k = 0; k < 5; ++k) v[k] += p[k];
   }
-  wm_block_sum<5>(v, red);
+  ctts_block_tree_sum<5, WM_THREADS>(v, red);
   if (tid == 0) {
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     double r = nan;
