@@ -75,6 +75,15 @@ class VconvDesc(C.Structure):
     ]
 
 
+class VconvMelganDesc(C.Structure):
+    """ctts_vconv_melgan_desc of include/ctts.h: the layer (`conv`) and MelGAN's extensions behind it"""
+    _fields_ = [
+        ("conv", VconvDesc),
+        ("pad_mode", _i32),
+        ("x2", _vp), ("sx2b", _i64), ("sx2t", _i64), ("Cin2", _i32),
+    ]
+
+
 class VconvHDesc(C.Structure):
     """ctts_vconv_h_desc of include/ctts.h (the fp16 mode's descriptor; ctypes zero-initialises it)"""
     _fields_ = [
@@ -191,6 +200,8 @@ _SIGNATURES = {
     "ctts_vocoder_conv": [C.POINTER(VconvDesc), _vp],
     "ctts_vocoder_post": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _f32, _vp, _vp],
     "ctts_vocoder_post_ragged": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _f32, _vp, _vp, C.c_int, _vp],
+    "ctts_vocoder_conv_melgan": [C.POINTER(VconvMelganDesc), _vp],
+    "ctts_vocoder_post_reflect": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _f32, _vp, _vp, C.c_int, _vp],
     "ctts_vocoder_conv_h": [C.POINTER(VconvHDesc), _vp],
     "ctts_vocoder_post_h": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _f32, _vp, _vp, C.c_int, _vp],
     "ctts_fastformer_pool_fwd": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, _vp],

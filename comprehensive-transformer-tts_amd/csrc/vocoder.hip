@@ -18,6 +18,10 @@
 //   and the transposed conv's row range and phase scatter; a tile at or beyond its utterance's end returns before it stages anything.
 //   The grid is still sized by the padded T and anchored at row 0 of each utterance, so a tile computes bit for bit what the same tile
 //   of a B = 1 call on the unpadded utterance computes.  Rows beyond Tb are not stored (nothing reads them).
+//   MelGAN (include/ctts.h, MelGAN block; melgan.py) runs on the same kernel body instantiated with MG = true: a row outside [0, Tb) is
+//   staged from its reflection about the utterance's own ends instead of as zeros, and a 1x1 conv may continue its K loop over the
+//   chunks of a second, un-activated input (the ResnetBlock's shortcut).  The MG = false instantiations are HiFi-GAN's, unchanged
+//   (profiles/melgan_isa.md).
 #include "vocoder_common.h"
 #include "planes_common.h"
 
@@ -41,11 +45,22 @@ struct VcParams {
   const float* x; long sxb, sxt, sxc; int vec;
 };
 
+// MelGAN's two extensions (include/ctts.h, MelGAN block) ride behind the HiFi-GAN arguments: the MG = false kernels never see them
+struct VcParamsMg {
+  VcParams p;
+  int reflect;                              // pad_mode: input rows outside [0, Tb) are read at their reflection
+  const float* x2; long sx2b, sx2t; int Cin2, cin2_pad, vec2;     // second operand of a 1x1 conv (NULL: none), dense channels
+};
+__device__ __forceinline__ const VcParams& vc_base(const VcParams& a) { return a; }
+__device__ __forceinline__ const VcParams& vc_base(const VcParamsMg& a) { return a.p; }
+
 __device__ __forceinline__ int x6sw(int row, int c) { return c ^ ((row >> 2) & 3); }
 __device__ __forceinline__ int f32sw(int row, int c) { return c ^ ((row >> 1) & 7); }
 
-template <bool X6, int BN>
-__global__ __launch_bounds__(256, 2) void vconv_kernel(const VcParams p) {
+// MG = false: HiFi-GAN's kernels, the code they always were.  MG = true (P = VcParamsMg): reflect padding and the two-operand K loop.
+template <bool X6, int BN, bool MG, class P>
+__global__ __launch_bounds__(256, 2) void vconv_kernel(const P pa) {
+  const VcParams& p = vc_base(pa);
   constexpr int NT = BN == 128 ? 2 : 1;
   constexpr int WAVES_N = BN / (32 * NT);             // 2, 2, 1
   constexpr int WAVES_M = 4 / WAVES_N;                // 2, 2, 4
@@ -64,8 +79,12 @@ __global__ __launch_bounds__(256, 2) void vconv_kernel(const VcParams p) {
   const int Tb = vc_rows(g.lens, b, g.len_mul, g.T), Mb = Tb + g.mextra, Toutb = g.u ? Tb * g.u : Tb;
   if (Tb == 0 || m0 >= Mb) return;
   const int p0 = g.row_off + m0;                      // position of tile row 0
-  const int nchunks = g.cin_pad >> 5, taps = g.taps;
-  const long kp = (long)taps * g.cin_pad;             // packed weight row length
+  const int nchunks1 = g.cin_pad >> 5, taps = g.taps;
+  int nchunks_ = nchunks1;
+  long kp_ = (long)taps * g.cin_pad;
+  if constexpr (MG) { nchunks_ += pa.cin2_pad >> 5; kp_ += pa.cin2_pad; }      // cin2_pad = 0 without x2; with it taps = 1
+  const int nchunks = nchunks_;                       // K chunks: those of x, then those of x2
+  const long kp = kp_;                                // packed weight row length
   const int arows = VC_BM + (taps - 1) * g.dil;
   const float* xb = p.x + (long)b * p.sxb;
 
@@ -110,24 +129,28 @@ __global__ __launch_bounds__(256, 2) void vconv_kernel(const VcParams p) {
     }
   };
   // input rows p0 + in_off + i (i < arows), channels chunk * 32 .. + 31, activated, zero outside [0, T) x [0, Cin)   (T = the utterance's Tb)
-  auto stage_a = [&](int chunk) {
+  // MG: under reflect a row outside [0, Tb) is read at its reflection (Tb the utterance's own); a chunk at or beyond nchunks1 is x2's
+  auto stage_rows = [&](int chunk, const float* xs, long sxt, long sxc, int vec, int cin, int act) {
     const int c4 = tid & 7, cbase = chunk * 32 + c4 * 4;
     for (int i = tid >> 3; i < arows; i += 32) {
-      const int ti = p0 + g.in_off + i;
+      int ti = p0 + g.in_off + i;
+      if constexpr (MG) {
+        if (pa.reflect) ti = ctts_reflect_index(ti, Tb);
+      }
       float v[4] = {0.f, 0.f, 0.f, 0.f};
       if (ti >= 0 && ti < Tb) {
-        const float* src = xb + (long)ti * p.sxt;
-        if (p.vec) {
-          if (cbase < g.Cin) {
+        const float* src = xs + (long)ti * sxt;
+        if (vec) {
+          if (cbase < cin) {
             const float4 f = *reinterpret_cast<const float4*>(src + cbase);
             v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
           }
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            if (cbase + e < g.Cin) v[e] = src[(long)(cbase + e) * p.sxc];
+            if (cbase + e < cin) v[e] = src[(long)(cbase + e) * sxc];
         }
-        if (g.act_in) {
+        if (act) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * g.slope;
         }
@@ -204,6 +227,13 @@ __global__ __launch_bounds__(256, 2) void vconv_kernel(const VcParams p) {
     }
   };
 
+  auto stage_a = [&](int chunk) {
+    if constexpr (MG) {
+      if (chunk >= nchunks1) { stage_rows(chunk - nchunks1, pa.x2 + (long)b * pa.sx2b, pa.sx2t, 1, pa.vec2, pa.Cin2, 0); return; }
+    }
+    stage_rows(chunk, xb, p.sxt, p.sxc, p.vec, g.Cin, g.act_in);
+  };
+
   load_b(0);
   for (int chunk = 0; chunk < nchunks; ++chunk) {
     __syncthreads();                       // every wave is done with the previous chunk's tiles
@@ -233,11 +263,21 @@ __global__ __launch_bounds__(256, 2) void vconv_kernel(const VcParams p) {
   });
 }
 
-}  // namespace
+template <bool MG, class P>
+void vconv_launch(bool x6, int BN, dim3 grid, hipStream_t st, const P& p) {
+  if (x6) {
+    if (BN == 128) hipLaunchKernelGGL((vconv_kernel<true, 128, MG, P>), grid, dim3(256), 0, st, p);
+    else if (BN == 64) hipLaunchKernelGGL((vconv_kernel<true, 64, MG, P>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((vconv_kernel<true, 32, MG, P>), grid, dim3(256), 0, st, p);
+  } else {
+    if (BN == 128) hipLaunchKernelGGL((vconv_kernel<false, 128, MG, P>), grid, dim3(256), 0, st, p);
+    else if (BN == 64) hipLaunchKernelGGL((vconv_kernel<false, 64, MG, P>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((vconv_kernel<false, 32, MG, P>), grid, dim3(256), 0, st, p);
+  }
+}
 
-extern "C" int ctts_vocoder_conv(const ctts_vconv_desc* dp, void* stream) {
-  CTTS_REQUIRE(dp, "ctts_vocoder_conv: NULL descriptor");
-  const ctts_vconv_desc& d = *dp;
+// the one launcher behind ctts_vocoder_conv (m == NULL) and ctts_vocoder_conv_melgan (m: its descriptor, d = m->conv)
+int vconv_run(const ctts_vconv_desc& d, const ctts_vconv_melgan_desc* m, void* stream) {
   CTTS_REQUIRE(d.x && d.w && d.out, "ctts_vocoder_conv: x, w and out are required");
   VcParams p{};
   int BN;
@@ -252,17 +292,38 @@ extern "C" int ctts_vocoder_conv(const ctts_vconv_desc* dp, void* stream) {
   p.vec = d.sxc == 1 && d.Cin % 4 == 0 && d.sxt % 4 == 0 && d.sxb % 4 == 0 && ((uintptr_t)d.x & 15) == 0;
   const dim3 grid = vc_grid(p.g, VC_BM, BN, d.B);
   hipStream_t st = (hipStream_t)stream;
-  if (x6) {
-    if (BN == 128) hipLaunchKernelGGL((vconv_kernel<true, 128>), grid, dim3(256), 0, st, p);
-    else if (BN == 64) hipLaunchKernelGGL((vconv_kernel<true, 64>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((vconv_kernel<true, 32>), grid, dim3(256), 0, st, p);
-  } else {
-    if (BN == 128) hipLaunchKernelGGL((vconv_kernel<false, 128>), grid, dim3(256), 0, st, p);
-    else if (BN == 64) hipLaunchKernelGGL((vconv_kernel<false, 64>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((vconv_kernel<false, 32>), grid, dim3(256), 0, st, p);
+  CTTS_REQUIRE(!m || m->pad_mode == 0 || m->pad_mode == 1, "ctts_vocoder_conv_melgan: pad_mode must be 0 (zero) or 1 (reflect), got %d",
+               m ? m->pad_mode : 0);
+  if (!m || (m->pad_mode == 0 && !m->x2)) {
+    vconv_launch<false>(x6, BN, grid, st, p);
+  } else {                                   // reflect padding and / or the second operand of a 1x1 conv
+    CTTS_REQUIRE(d.transposed_u == 0, "ctts_vocoder_conv_melgan: pad_mode = 1 and x2 are for Conv1d only (transposed_u=%d)", d.transposed_u);
+    CTTS_REQUIRE(!m->pad_mode || d.T > (d.k - 1) * d.dil / 2,
+                 "ctts_vocoder_conv_melgan: reflection needs T > dil (k - 1) / 2 (T=%d k=%d dil=%d)", d.T, d.k, d.dil);
+    VcParamsMg q{};
+    q.p = p; q.reflect = m->pad_mode;
+    if (m->x2) {
+      CTTS_REQUIRE(d.k == 1 && m->Cin2 >= 1, "ctts_vocoder_conv_melgan: x2 needs k == 1 and Cin2 >= 1 (k=%d Cin2=%d)", d.k, m->Cin2);
+      CTTS_REQUIRE(d.out != m->x2, "ctts_vocoder_conv_melgan: out must not alias x2");
+      q.x2 = m->x2; q.sx2b = m->sx2b; q.sx2t = m->sx2t; q.Cin2 = m->Cin2; q.cin2_pad = (m->Cin2 + 31) / 32 * 32;
+      q.vec2 = m->Cin2 % 4 == 0 && m->sx2t % 4 == 0 && m->sx2b % 4 == 0 && ((uintptr_t)m->x2 & 15) == 0;
+    }
+    vconv_launch<true>(x6, BN, grid, st, q);
   }
   CTTS_CHECK_LAUNCH("ctts_vocoder_conv");
   return 0;
+}
+
+}  // namespace
+
+extern "C" int ctts_vocoder_conv(const ctts_vconv_desc* dp, void* stream) {
+  CTTS_REQUIRE(dp, "ctts_vocoder_conv: NULL descriptor");
+  return vconv_run(*dp, nullptr, stream);
+}
+
+extern "C" int ctts_vocoder_conv_melgan(const ctts_vconv_melgan_desc* dp, void* stream) {
+  CTTS_REQUIRE(dp, "ctts_vocoder_conv_melgan: NULL descriptor");
+  return vconv_run(dp->conv, dp, stream);
 }
 
 extern "C" int ctts_vocoder_post(const float* x, int B, int T, int C, int k, const float* w, const float* bias, float slope, float* out,
@@ -274,4 +335,9 @@ extern "C" int ctts_vocoder_post_ragged(const float* x, int B, int T, int C, int
                                         float* out, const int32_t* lens, int len_mul, void* stream) {
   CTTS_REQUIRE(lens && len_mul >= 1, "ctts_vocoder_post_ragged: lens and len_mul >= 1 are required (len_mul=%d)", len_mul);
   return vpost_launch("ctts_vocoder_post_ragged", x, B, T, C, k, w, bias, slope, out, lens, len_mul, stream);
+}
+
+extern "C" int ctts_vocoder_post_reflect(const float* x, int B, int T, int C, int k, const float* w, const float* bias, float slope,
+                                         float* out, const int32_t* lens, int len_mul, void* stream) {
+  return vpost_launch<float, true>("ctts_vocoder_post_reflect", x, B, T, C, k, w, bias, slope, out, lens, lens ? len_mul : 1, stream);
 }

@@ -3,6 +3,7 @@
 // Everything here has internal linkage: the library's exports are those of include/ctts.h.
 #pragma once
 #include "ctts_common.h"
+#include "fft_common.h"                    // ctts_reflect_index
 
 namespace {
 
@@ -93,7 +94,8 @@ constexpr int VP_ROWS = 256, VP_PITCH = 33;
 // conv_post (Cout = 1, models.py:161-163): leaky_relu on load, k-tap dot product on the VALU in fp32, + bias, tanh, fp32 out.
 // out[b, 0, t] = tanh(bias + sum_{tap, c} leaky_relu(float(x[b, t + tap - (k - 1) / 2, c]), slope) w[tap][c]); x [B, T, C] dense
 // ragged (lens != NULL): rows at or beyond Tb = min(lens[b] len_mul, T) read as zero and out[b, 0, Tb ..] = 0
-template <class TIn>
+// REFLECT (MelGAN's ReflectionPad1d in front of the last conv): a row outside [0, Tb) is read at its reflection about the utterance's ends
+template <class TIn, bool REFLECT = false>
 __global__ __launch_bounds__(256) void vpost_kernel(const TIn* __restrict__ x, int T, int C, int k, const float* __restrict__ w,
                                                     const float* __restrict__ bias, float slope, float* __restrict__ out,
                                                     const int* __restrict__ lens, int len_mul) {
@@ -110,7 +112,9 @@ __global__ __launch_bounds__(256) void vpost_kernel(const TIn* __restrict__ x, i
   for (int c0 = 0; c0 < C; c0 += 32) {
     __syncthreads();
     for (int e = tid; e < rows * 32; e += 256) {
-      const int r = e >> 5, c = e & 31, t = t0 - half + r;
+      const int r = e >> 5, c = e & 31;
+      int t = t0 - half + r;
+      if constexpr (REFLECT) t = ctts_reflect_index(t, Tb);
       float v = 0.f;
       if (t >= 0 && t < Tb && c0 + c < C) {
         v = (float)xb[(long)t * C + c0 + c];
@@ -131,7 +135,7 @@ __global__ __launch_bounds__(256) void vpost_kernel(const TIn* __restrict__ x, i
 }
 
 // the one launcher behind ctts_vocoder_post / _post_ragged / _post_h (lens == NULL: dense)
-template <class TIn>
+template <class TIn, bool REFLECT = false>
 int vpost_launch(const char* what, const TIn* x, int B, int T, int C, int k, const float* w, const float* bias, float slope, float* out,
                  const int32_t* lens, int len_mul, void* stream) {
   CTTS_REQUIRE(x && w && bias && out && B >= 1 && T >= 1 && C >= 1 && k >= 1 && k % 2 == 1, "%s: bad arguments (B=%d T=%d C=%d k=%d)", what,
@@ -139,8 +143,9 @@ int vpost_launch(const char* what, const TIn* x, int B, int T, int C, int k, con
   CTTS_REQUIRE(!lens || len_mul >= 1, "%s: lens needs len_mul >= 1 (len_mul=%d)", what, len_mul);
   const size_t lds = (size_t)(VP_ROWS + k - 1) * VP_PITCH * sizeof(float);
   CTTS_REQUIRE(lds <= 64 * 1024, "%s: k=%d too large", what, k);
+  CTTS_REQUIRE(!REFLECT || T > (k - 1) / 2, "%s: reflection needs T > (k - 1) / 2 (T=%d k=%d)", what, T, k);
   dim3 grid((T + VP_ROWS - 1) / VP_ROWS, B);
-  hipLaunchKernelGGL(vpost_kernel<TIn>, grid, dim3(256), lds, (hipStream_t)stream, x, T, C, k, w, bias, slope, out, lens, len_mul);
+  hipLaunchKernelGGL((vpost_kernel<TIn, REFLECT>), grid, dim3(256), lds, (hipStream_t)stream, x, T, C, k, w, bias, slope, out, lens, len_mul);
   CTTS_CHECK_LAUNCH(what);
   return 0;
 }

@@ -1313,11 +1313,25 @@ def mel_spectrogram_fft(y, window, ws, n_fft, hop, n_mel, clip=1e-5, want_mag=Fa
 
 
 # ---- HiFi-GAN vocoder (csrc/vocoder.hip) ------------------------------------------------------------------------------------
-def vocoder_pack_weight(weight, transposed_u=0, planes=None):
+def vocoder_pack_weight(weight, transposed_u=0, planes=None, weight2=None):
     """Folded Conv1d weight [Cout, Cin, k] (transposed_u = 0) or ConvTranspose1d weight [Cin, Cout, k] (transposed_u = u) -> the packed
     operand of ctts_vocoder_conv: (w [roundup(N, 128), taps * roundup(Cin, 32)] fp32, w_planes or None).  `planes`: also split it
-    (ctts_split_planes; None = the module default BF16_SPLIT).  Weight packing is a one-time layout change of a constant."""
+    (ctts_split_planes; None = the module default BF16_SPLIT).  Weight packing is a one-time layout change of a constant.
+    `weight2` [Cout, Cin2, 1] (with a 1x1 Conv1d `weight` only): the two-operand form of vocoder_conv(..., x2=) -
+    w [roundup(Cout, 128), roundup(Cin, 32) + roundup(Cin2, 32)], weight's columns first."""
     w = weight.detach().float()
+    if weight2 is not None:
+        w2 = weight2.detach().float()
+        if transposed_u or w.dim() != 3 or w2.dim() != 3 or w.shape[2] != 1 or w2.shape[2] != 1 or w2.shape[0] != w.shape[0]:
+            raise _lib.CttsError(f"vocoder_pack_weight: the two-operand form needs two 1x1 Conv1d weights of one Cout, got "
+                                 f"{tuple(w.shape)} and {tuple(w2.shape)}")
+        N, c1, c2 = w.shape[0], w.shape[1], w2.shape[1]
+        npad, p1, p2 = -(-N // 128) * 128, -(-c1 // 32) * 32, -(-c2 // 32) * 32
+        packed = torch.zeros(npad, p1 + p2, dtype=torch.float32, device=w.device)
+        packed[:N, :c1] = w[:, :, 0]
+        packed[:N, p1:p1 + c2] = w2[:, :, 0]
+        use = BF16_SPLIT if planes is None else planes
+        return packed, (split_planes([packed])[0] if use else None)
     if transposed_u:
         cin, cout, k = w.shape
         u = int(transposed_u)
@@ -1352,10 +1366,12 @@ def _f16c(t, name):
     return t
 
 
-def _vocoder_conv_desc(what, d, dtype, names, x, w, Cin, Cout, k, dil, transposed_u, slope, bias, R, out, alpha, beta, lens, len_mul):
+def _vocoder_conv_desc(what, d, dtype, names, x, w, Cin, Cout, k, dil, transposed_u, slope, bias, R, out, alpha, beta, lens, len_mul,
+                       Cin2=0):
     """What vocoder_conv and vocoder_conv_h share (`what`: the wrapper's name, for the messages; x already checked for dtype and rank):
     the shape, `out`, R, packed-weight and same-device checks, and the descriptor fields the two structs have in common.  `dtype` is
-    the wrapper's type of w, R and out (float32 / float16), `names` its message names for them.  -> out, allocated when not given."""
+    the wrapper's type of w, R and out (float32 / float16), `names` its message names for them.  Cin2: the channels of vocoder_conv's
+    second operand, which widen the packed weight.  -> out, allocated when not given."""
     act = _f32c if dtype == torch.float32 else _f16c
     B, T, cin = x.shape
     if cin != Cin:
@@ -1370,7 +1386,7 @@ def _vocoder_conv_desc(what, d, dtype, names, x, w, Cin, Cout, k, dil, transpose
     if R is not None and tuple(R.shape) != (B, Tout, Cout):
         raise _lib.CttsError(f"{what}: R has shape {tuple(R.shape)}, expected {(B, Tout, Cout)}")
     N, taps = (transposed_u * Cout, k // transposed_u) if transposed_u else (Cout, k)
-    wshape = (-(-N // 128) * 128, taps * (-(-Cin // 32) * 32))
+    wshape = (-(-N // 128) * 128, taps * (-(-Cin // 32) * 32) + -(-Cin2 // 32) * 32)
     if tuple(act(w, names[0]).shape) != wshape:
         raise _lib.CttsError(f"{what}: packed weight {tuple(w.shape)} does not match the layer (expected {wshape})")
     for t, name in ((w, "weight"), (bias, "bias"), (R, "R"), (out, "out")):
@@ -1391,35 +1407,75 @@ def _vocoder_conv_desc(what, d, dtype, names, x, w, Cin, Cout, k, dil, transpose
     return out
 
 
+VOCODER_PAD_MODES = {"zero": 0, "reflect": 1}          # ctts_vconv_melgan_desc.pad_mode
+
+
+def _vocoder_pad_mode(pad_mode, what):
+    if pad_mode not in VOCODER_PAD_MODES:
+        raise _lib.CttsError(f"{what}: pad_mode must be one of {tuple(VOCODER_PAD_MODES)}, got {pad_mode!r}")
+    return VOCODER_PAD_MODES[pad_mode]
+
+
 def vocoder_conv(x, w, w_planes, Cin, Cout, k, dil=1, transposed_u=0, slope=None, bias=None, R=None, out=None, alpha=1.0, beta=0.0,
-                 bf16_split=None, lens=None, len_mul=1):
-    """One generator layer (include/ctts.h ctts_vocoder_conv).  x: [B, T, Cin] with any strides (fp32); w / w_planes from
+                 bf16_split=None, lens=None, len_mul=1, pad_mode="zero", x2=None):
+    """One generator layer (include/ctts.h ctts_vocoder_conv; with pad_mode="reflect" or x2, ctts_vocoder_conv_melgan).  x: [B, T, Cin] with any strides (fp32); w / w_planes from
     vocoder_pack_weight; slope: leaky_relu slope applied to x on load, or None.  -> out [B, T_out, Cout] (T_out = T or T u):
     out = beta * out + alpha * (conv + bias + R).  lens (device int32 [B]) / len_mul: the length-aware form - utterance b's input has
-    min(lens[b] len_mul, T) rows, computed as a B = 1 call on them would; output rows beyond its end are left unwritten."""
+    min(lens[b] len_mul, T) rows, computed as a B = 1 call on them would; output rows beyond its end are left unwritten.
+    MelGAN (include/ctts.h, MelGAN block): pad_mode="reflect" puts ReflectionPad1d(dil (k - 1) / 2) in place of the zero padding (Conv1d
+    only, T above the padding), reflecting at each utterance's own end; x2 [B, T, Cin2] (k = 1 only, unit channel stride) is a second
+    operand that is never activated: out = W [act(x) ; x2] + ..., w from vocoder_pack_weight(weight, weight2=)."""
     if x.dtype != torch.float32 or x.dim() != 3:
         raise _lib.CttsError(f"vocoder_conv: x must be a 3-D float32 tensor [B, T, Cin], got {x.dtype} {tuple(x.shape)}")
     split = BF16_SPLIT if bf16_split is None else int(bf16_split)
     if split and w_planes is None:
         raise _lib.CttsError("vocoder_conv: the split arithmetic needs w_planes")
-    d = _lib.VconvDesc()
+    mode = _vocoder_pad_mode(pad_mode, "vocoder_conv")
+    if mode and transposed_u:
+        raise _lib.CttsError("vocoder_conv: pad_mode='reflect' is for Conv1d only (transposed_u must be 0)")
+    if mode and x.shape[1] <= (k - 1) * dil // 2:
+        raise _lib.CttsError(f"vocoder_conv: reflection needs T > dil (k - 1) / 2 = {(k - 1) * dil // 2}, got T = {x.shape[1]}")
+    cin2 = 0
+    if x2 is not None:
+        if k != 1 or transposed_u:
+            raise _lib.CttsError(f"vocoder_conv: x2 is for a 1x1 Conv1d only (k={k}, transposed_u={transposed_u})")
+        if not (torch.is_tensor(x2) and x2.dtype == torch.float32 and x2.dim() == 3 and tuple(x2.shape[:2]) == tuple(x.shape[:2])
+                and x2.stride(2) == 1 and x2.device == x.device):
+            raise _lib.CttsError(f"vocoder_conv: x2 must be a float32 [B, T, Cin2] tensor on x's device with x's B and T and unit "
+                                 f"channel stride, got {getattr(x2, 'dtype', type(x2))} {tuple(getattr(x2, 'shape', ()))}")
+        cin2 = int(x2.shape[2])
+    md = _lib.VconvMelganDesc() if mode or x2 is not None else None
+    d = _lib.VconvDesc() if md is None else md.conv
     out = _vocoder_conv_desc("vocoder_conv", d, torch.float32, ("vocoder weight", "R", "out"), x, w, Cin, Cout, k, dil, transposed_u, slope,
-                             bias, R, out, alpha, beta, lens, len_mul)
+                             bias, R, out, alpha, beta, lens, len_mul, Cin2=cin2)
     if split and w_planes.numel() != 3 * w.numel():          # w has the layer's shape by now: the planes are not its split
         raise _lib.CttsError(f"vocoder_conv: packed weight {tuple(w.shape)} does not match the layer (expected {tuple(w.shape)})")
     d.w_planes = _p(w_planes) if split else None
     d.bf16_split = split
-    _lib.check(_lib.load().ctts_vocoder_conv(C.byref(d), _stream()), "ctts_vocoder_conv")
+    if md is None:
+        _lib.check(_lib.load().ctts_vocoder_conv(C.byref(d), _stream()), "ctts_vocoder_conv")
+        return out
+    md.pad_mode = mode
+    if x2 is not None:
+        md.x2, md.sx2b, md.sx2t, md.Cin2 = _p(x2), int(x2.stride(0)), int(x2.stride(1)), cin2
+    _lib.check(_lib.load().ctts_vocoder_conv_melgan(C.byref(md), _stream()), "ctts_vocoder_conv_melgan")
     return out
 
 
-def vocoder_post(x, w, bias, slope=0.01, out=None, lens=None, len_mul=1):
+def vocoder_post(x, w, bias, slope=0.01, out=None, lens=None, len_mul=1, pad_mode="zero"):
     """conv_post + tanh (include/ctts.h ctts_vocoder_post): x [B, T, C] dense, w [k, C] (= weight[0].T), bias [1] -> [B, 1, T].
-    lens (device int32 [B]) / len_mul: ctts_vocoder_post_ragged - out[b, 0, lens[b] len_mul:] = 0, rows there are never read."""
+    lens (device int32 [B]) / len_mul: ctts_vocoder_post_ragged - out[b, 0, lens[b] len_mul:] = 0, rows there are never read.
+    pad_mode="reflect": ctts_vocoder_post_reflect (MelGAN's ReflectionPad1d((k - 1) / 2) in front of the conv; dense or ragged)."""
     B, T, Cc = x.shape
     k = w.shape[0]
     if out is None:
         out = torch.empty(B, 1, T, dtype=torch.float32, device=x.device)
+    if _vocoder_pad_mode(pad_mode, "vocoder_post"):
+        lp, lm = _vocoder_lens(lens, len_mul, B, "vocoder_post")
+        _lib.check(_lib.load().ctts_vocoder_post_reflect(_p(_f32c(x, "x")), B, T, Cc, int(k), _p(_f32c(w, "w")), _p(_f32c(bias, "bias")),
+                                                         float(slope), _p(_f32c(out, "out")), lp, lm, _stream()),
+                   "ctts_vocoder_post_reflect")
+        return out
     if lens is not None:
         lp, lm = _vocoder_lens(lens, len_mul, B, "vocoder_post")
         _lib.check(_lib.load().ctts_vocoder_post_ragged(_p(_f32c(x, "x")), B, T, Cc, int(k), _p(_f32c(w, "w")), _p(_f32c(bias, "bias")),

@@ -200,8 +200,9 @@ class Generator(nn.Module):
         return self._forward(x, lens=lens, precision=self._call_precision)
 
     @staticmethod
-    def _device_lens(lens, x):
-        """`lens` of forward() -> a contiguous device int32 [B] tensor.  A device int32 tensor goes in as it is (the kernels clamp it to
+    def _device_lens(lens, x, what="hifigan Generator"):
+        """`lens` of forward() -> a contiguous device int32 [B] tensor (`what`: the caller's name, for the messages; melgan.Generator
+        shares this).  A device int32 tensor goes in as it is (the kernels clamp it to
         [0, T]); a device int64 tensor (the acoustic model's mel_lens) is clamped and narrowed on the device, no sync; a list or a CPU
         tensor is copied to the device once.  Raises CttsError for a wrong shape or a non-integer dtype, before any launch."""
         B, T = x.shape[0], x.shape[2]
@@ -209,14 +210,14 @@ class Generator(nn.Module):
             try:
                 lens = torch.as_tensor(lens)
             except Exception as e:
-                raise _lib.CttsError(f"hifigan Generator: lens must be a tensor or a list of integers ({e})") from None
+                raise _lib.CttsError(f"{what}: lens must be a tensor or a list of integers ({e})") from None
         if lens.dtype not in (torch.int32, torch.int64):
-            raise _lib.CttsError(f"hifigan Generator: lens must be int32 or int64, got {lens.dtype}")
+            raise _lib.CttsError(f"{what}: lens must be int32 or int64, got {lens.dtype}")
         if tuple(lens.shape) != (B,):
-            raise _lib.CttsError(f"hifigan Generator: lens must have shape ({B},) for a mel {tuple(x.shape)}, got {tuple(lens.shape)}")
+            raise _lib.CttsError(f"{what}: lens must have shape ({B},) for a mel {tuple(x.shape)}, got {tuple(lens.shape)}")
         if lens.device != x.device:
             if lens.is_cuda:
-                raise _lib.CttsError(f"hifigan Generator: lens is on {lens.device}, the mel on {x.device}")
+                raise _lib.CttsError(f"{what}: lens is on {lens.device}, the mel on {x.device}")
             lens = lens.to(x.device)
         if lens.dtype == torch.int64:
             lens = lens.clamp(0, T).to(torch.int32)

@@ -655,6 +655,34 @@ int ctts_vocoder_post_ragged(const float* x, int B, int T, int C, int k, const f
                              const int32_t* lens, int len_mul, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * MelGAN vocoder, inference (comprehensive-transformer-tts_amd/melgan.py; the generator of descriptinc/melgan-neurips
+ * mel2wav/modules.py, which utils/model.py:42-92 fetches through torch.hub for `vocoder.model: "MelGAN"`).  It runs on
+ * ctts_vocoder_conv_melgan - ctts_vocoder_conv's kernels, layer description (`conv`), arithmetic and ragged contract, with two
+ * extensions that ride behind it in a descriptor of their own (ctts_vconv_desc keeps its layout: the ABI version does not move) - and
+ * on a reflecting conv_post.  All fields 0 / NULL: exactly ctts_vocoder_conv(&conv).
+ *   pad_mode = 1 (transposed_u == 0 only): the Conv1d is preceded by ReflectionPad1d(dil (k - 1) / 2) instead of zero padding: input
+ *     row ti outside [0, Tb) is read at -ti or 2 (Tb - 1) - ti, where Tb is the utterance's OWN row count (T, or the ragged
+ *     min(lens[b] len_mul, T)), so utterance b is still computed bit for bit as its B = 1 call and rows at or beyond Tb are never
+ *     read.  DOMAIN: Tb > dil (k - 1) / 2, as for torch's ReflectionPad1d; a dense T at or below the padding is rejected, a shorter
+ *     device-given length has its reflected rows clamped into [0, Tb) - memory-safe, not a reflection.
+ *   x2 != NULL (k == 1, transposed_u == 0 only): a 1x1 conv of TWO inputs, out = W [act(x) ; x2] (+ bias, R, alpha / beta as above):
+ *     the K loop runs over the 32-channel chunks of x (activated as act_in says), then over those of x2 [B, T, Cin2] (element
+ *     (b, t, c) at x2[b sx2b + t sx2t + c], never activated); w is [roundup(Cout, 128)][1][roundup(Cin, 32) + roundup(Cin2, 32)],
+ *     x's columns first.  One GEMM of K = Cin + Cin2 for the ResnetBlock's `shortcut(x) + block(x)`: W = [W_block.4 | W_shortcut],
+ *     bias = their sum.  out must alias neither input.  conv.w_planes: the split of that whole matrix.
+ *   ctts_vocoder_post_reflect: ctts_vocoder_post / _post_ragged (lens may be NULL: dense) with ReflectionPad1d((k - 1) / 2) in
+ *     front of the conv, reflecting at the utterance's own end; exact zeros from row Tb on.  Same domain as pad_mode = 1.
+ *   Arithmetic, ragged contract and bit-reproducibility are those of the HiFi-GAN block above. */
+typedef struct ctts_vconv_melgan_desc {
+  ctts_vconv_desc conv;
+  int32_t pad_mode;
+  const float* x2; int64_t sx2b, sx2t; int32_t Cin2;
+} ctts_vconv_melgan_desc;
+int ctts_vocoder_conv_melgan(const ctts_vconv_melgan_desc* d, void* stream);
+int ctts_vocoder_post_reflect(const float* x, int B, int T, int C, int k, const float* w, const float* bias, float slope, float* out,
+                              const int32_t* lens, int len_mul, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * HiFi-GAN vocoder, fp16 mode (csrc/vocoder_h.hip; vocoder.Generator called as g(mel, lens, precision="fp16")).  The same layers, shapes,
  * weight layout (ConvTranspose1d polyphase form included), epilogue and ragged contract as ctts_vocoder_conv / ctts_vocoder_post above;
  * what differs is the number format.  The fp32 entry points and ctts_vconv_desc are untouched by it.  Arithmetic contract:
