@@ -354,7 +354,9 @@ __global__ __launch_bounds__(256) void f0_targets_kernel(const float* __restrict
   const float gmin = fminf(fminf(redf[0], redf[1]), fminf(redf[2], redf[3])), gmax = fmaxf(fmaxf(redf[4], redf[5]), fmaxf(redf[6], redf[7]));
   const float meanf = (float)mean, stdf = (float)sqrt(var);
   const int any_bad = __syncthreads_or((int)bad);
-  bool ok = any_voiced && !any_bad && gmax > gmin && fabsf(meanf) < INFINITY && stdf > 0.f && stdf < INFINITY;     // block-uniform
+  // n == 2 has M = 2, where pycwt's w_1 = 2 pi fftfreq(2, dt)[1] is the Nyquist bin and negative: its sqrt(s_j w_1 M) is NaN for every
+  // scale, a non-finite output like any other (the closed form sqrt(4 pi 2^j) below holds for M >= 4 only)
+  bool ok = any_voiced && !any_bad && n > 2 && gmax > gmin && fabsf(meanf) < INFINITY && stdf > 0.f && stdf < INFINITY;     // block-uniform
   if (ok) {
     int logM = 0;
     while ((1 << logM) < n) ++logM;                      // n <= 4096: at most 12 steps

@@ -60,8 +60,8 @@ def track_pitch(wav, lens=None, **params):
 
 def f0_targets(f0, frames):
     """f0 [B,F] Hz (0 = unvoiced), frames [B] (device) -> dict(uv [B,F], cont_lf0 [B,F], f0_mean [B], f0_std [B], cwt_spec [B,F,10],
-    valid int32 [B]).  An utterance without a voiced frame, with a constant contour or with a non-finite result has valid = 0 and
-    all-zero rows; frames at or beyond frames[b] are zero."""
+    valid int32 [B]).  An utterance without a voiced frame, with a constant contour or with a non-finite result (which every utterance
+    of two frames has: pycwt's normalisation is NaN at M = 2) has valid = 0 and all-zero rows; frames at or beyond frames[b] are zero."""
     if not torch.is_tensor(f0) or not f0.is_cuda:
         raise CttsError("f0_targets computes on the MI355X: pass f0 as a device tensor - no CPU fallback exists")
     uv, cont, mean_std, cwt, valid = K.f0_targets(f0, _device_lens(frames, f0.shape[0], f0.device, "f0_targets"))

@@ -844,7 +844,8 @@ int ctts_allreduce_mean(float* buf, int64_t n, void* comm, void* stream);
  *   f0 [B,F] Hz (0 = unvoiced); frames [B] int32 (clamped to [0, F]); uv [B,F] = (f0 == 0) as 0 / 1 floats (the dataset's polarity,
  *   norm_interp_f0); cont_lf0 [B,F]; mean_std [B,2]; cwt_spec [B,F,10]; valid [B] int32.  valid = 0 - and every output row of the
  *   utterance 0 - when it has no voiced frame, when its cont_lf0 is constant (std == 0, decided exactly: max == min), or when any output
- *   is not finite.  Frames at or beyond frames[b] are 0 in every output.  DOMAIN: 1 <= F <= 4096 (refused otherwise), nscale = 10.
+ *   is not finite - which includes every utterance of two frames: at M = 2, w_1 = 2 pi fftfreq(2, dt)[1] is negative and sqrt(s_j w_1 M)
+ *   is NaN.  Frames at or beyond frames[b] are 0 in every output.  DOMAIN: 1 <= F <= 4096 (refused otherwise), nscale = 10.
  * ctts_norm_interp_f0: the model-side f0 target (utils/pitch_tools.py:39-66 with pitch_norm "log", use_uv): log2(f0 + eps), 0 at
  * unvoiced frames, then np.interp over the unvoiced positions (edge values held); all unvoiced -> zeros.  Same kernel, other mode. */
 size_t ctts_pitch_track_workspace_bytes(void);

@@ -22,7 +22,10 @@ CWT_DT, CWT_S0, CWT_J = 0.005, 0.01, 9
 
 # ---- measured on the inputs of tests/test_pitch_restate_cpu.py with the float64 restatement ------------------
 TRACKER_WORST_REL_ERR = 4.58e-4      # worst |f0 - true| / true over the voiced frames of the tones and the glide; the test asserts 2 x this
-DECISION_DELTA = 1.0e-6             # 4 x the largest |fp32 - fp64| candidate height on those inputs and the GPU test batches (4 x 1.74e-7, rounded up)
+TRACKER_TONES_WORST_REL_ERR = 6.43e-3  # the same over the 15 stationary tones of gpu_tracker_cases() (every rate, hop and pitch range; the worst is
+                                     # 110 Hz at 48 kHz, 2.3 periods per frame); the GPU test asserts 2 x this against the true frequency
+DECISION_DELTA = 1.2e-6             # 4 x the largest |fp32 - fp64| candidate height on those inputs, the GPU test batches and gpu_tracker_cases()
+                                     # (4 x 2.83e-7 = 1.13e-6, rounded up; the largest is the 110 Hz tone at 48 kHz)
 INVERSE_CWT_MIN_CORR = 0.912         # lowest Pearson correlation of inverse_cwt(W) with the normalised contour over the fixture tracks
 
 
@@ -71,8 +74,9 @@ def frame_candidates(x, dtype, sr=SR, f0_min=F0_MIN, f0_max=F0_MAX, use_octave_c
 
 
 def track_pitch(wav, lens=None, sr=SR, hop=HOP, f0_min=F0_MIN, f0_max=F0_MAX, voicing_threshold=VOICING, silence_threshold=SILENCE,
-                dtype=np.float64, use_octave_cost=True, details=None):
-    """wav [B,N] -> (f0 [B,F], strength [B,F]); `details` (a list) receives (b, t, lags, heights, costs, winner index) per analysed frame"""
+                dtype=np.float64, use_octave_cost=True, details=None, levels=None):
+    """wav [B,N] -> (f0 [B,F], strength [B,F]); `details` (a list) receives (b, t, lags, heights, costs, winner index) per analysed frame
+    that has a candidate, `levels` (a list) receives (b, t, frame peak, utterance peak) for the same frames"""
     wav = np.asarray(wav, dtype)
     B, N = wav.shape
     F = 1 + N // hop
@@ -94,6 +98,8 @@ def track_pitch(wav, lens=None, sr=SR, hop=HOP, f0_min=F0_MIN, f0_max=F0_MAX, vo
                 f0[b, t] = dtype(sr) / lag[w]
             if details is not None:
                 details.append((b, t, lag, h, cost, w))
+            if levels is not None:
+                levels.append((b, t, float(np.abs(x).max()), float(peak)))
     return f0, st
 
 
@@ -173,7 +179,8 @@ def cwt_mexican_hat(x, dtype=np.float64, wrong_norm=False):
     out = np.zeros((n, CWT_J + 1), dtype)
     for j, s in enumerate(cwt_scales()):
         s = dtype(s)
-        norm = np.sqrt(s * w[1] * dtype(M)) if not wrong_norm else np.sqrt(s)
+        with np.errstate(invalid="ignore"):              # M = 2: w[1] is the Nyquist bin, negative - NaN, as in pycwt
+            norm = np.sqrt(s * w[1] * dtype(M)) if not wrong_norm else np.sqrt(s)
         out[:, j] = np.fft.ifft(X * (norm * mexican_hat_ft(s * w)))[:n].real
     assert out.dtype == np.dtype(dtype)
     return out
@@ -285,6 +292,137 @@ def gpu_silence_batch():
     w = np.zeros((2, GPU_TRACK_N), np.float32)
     w[1] = harmonic_tone(140.0, GPU_TRACK_N).astype(np.float32)
     return w
+
+
+# ---- tracker inputs over the whole lag range, other rates / hops / pitch ranges and the two thresholds ------------------------------
+# Every case: wav float32 [B, N <= 6144], lens (or None), the keyword arguments of track_pitch, and per utterance the true F0 of a
+# stationary tone (None: not one).  tests/test_pitch_restate_cpu.py holds every case to the decision margins; the GPU test runs each as
+# one launch.  Lag = sr / f0 falls in lane lag mod 64, register m = lag // 64 of pitch_track_kernel.
+EDGE_TONES_HZ = (81.0, 84.0, 740.0)                         # winners at lags 270-272 and 261-263 (m = 4), 29.8 (lag_lo = 29, m = 0)
+RAGGED_LENS = (6000, 100, 7000, -5, 3333)                   # no multiple of hop; shorter than half a frame; > N and < 0 clamp
+PARAM_SETS = {
+    "sr16k": dict(sr=16000, hop=200, f0_min=60.0, f0_max=400.0),     # lags 40..267
+    "sr48k": dict(sr=48000, hop=512, f0_min=100.0, f0_max=1200.0),   # lags 40..480
+    "f0min50": dict(f0_min=50.0),                                    # lag_hi = 441: registers m = 5, 6
+}
+SILENCE_LOW, VOICING_LOW = 0.01, 0.4                         # the non-default thresholds of the two threshold cases
+SILENCE_STEP = 3000                                          # the sample at which the silence case's first utterance drops to 2 %
+VOICING_NOISE_SEED = 3                                       # keeps every frame within the margins of the CPU test; to be replaced if it stops
+
+
+def _garbage(rng, shape):
+    return np.clip(0.25 * rng.standard_normal(shape), -1, 1)
+
+
+def ragged_batch():
+    """[5, 6144] with RAGGED_LENS and NaN-free garbage past each length: a rising glide, 100 samples of a tone, a falling glide whose
+    length clamps to N, an utterance of clamped length 0, a tone with vibrato.  F = 25 is no multiple of a wave's four frames, so
+    utterance boundaries fall inside waves, and B F = 125 is no multiple of a workgroup's 16."""
+    n = GROUND_TRUTH_N
+    rng = np.random.default_rng(23)
+    w = _garbage(rng, (5, n))
+    n0, n1, _, _, n4 = RAGGED_LENS
+    w[0, :n0] = harmonic_tone(np.linspace(150.0, 260.0, n0), n0)
+    w[1, :n1] = harmonic_tone(300.0, n)[:n1]
+    w[2] = harmonic_tone(np.linspace(300.0, 200.0, n), n)
+    w[4, :n4] = harmonic_tone(180.0 * (1.0 + 0.08 * np.sin(2.0 * np.pi * 9.0 * np.arange(n4) / SR)), n4)
+    return w.astype(np.float32)
+
+
+def _voicing_input(seed=VOICING_NOISE_SEED):
+    """a 150 Hz tone in white noise of the tone's own power: the winner's height sits near 0.5"""
+    n = GROUND_TRUTH_N
+    x = harmonic_tone(150.0, n)
+    noise = np.random.default_rng(seed).standard_normal(n) * np.sqrt(np.mean(x * x))
+    return np.clip(0.6 * (x + noise), -1, 1)
+
+
+def _silence_input():
+    """[2, 6144]: a 200 Hz tone at peak 0.5 that drops to 2 % of it at SILENCE_STEP; a 260 Hz tone at peak 0.012 throughout, which is
+    above the silence threshold of its own peak and below 0.03 x the first utterance's"""
+    n = GROUND_TRUTH_N
+    w = np.stack([harmonic_tone(200.0, n), 0.024 * harmonic_tone(260.0, n)])
+    w[0, SILENCE_STEP:] *= 0.02
+    return w
+
+
+def gpu_tracker_cases():
+    """name -> dict(wav, lens, params, truth)"""
+    n = GROUND_TRUTH_N
+    gt = ground_truth_inputs()
+    c = {}
+
+    def add(name, wav, truth, lens=None, **params):
+        wav = np.ascontiguousarray(np.asarray(wav, np.float32))
+        c[name] = dict(wav=wav, lens=lens, params=params, truth=list(truth))
+
+    add("ground_truth", np.stack([w for w, _ in gt.values()]), [t[0] if t is not None and k.startswith("tone") else None for k, (_, t) in gt.items()])
+    add("edges", np.stack([harmonic_tone(f, n) for f in EDGE_TONES_HZ] + [harmonic_tone(200.0, n) + 0.3]), EDGE_TONES_HZ + (200.0,))
+    add("ragged", ragged_batch(), [None] * 5, lens=RAGGED_LENS)
+    add("ragged_sr16k", ragged_batch(), [None] * 5, lens=RAGGED_LENS, **PARAM_SETS["sr16k"])       # the same samples read at 16 kHz
+    p = PARAM_SETS["sr16k"]
+    add("sr16k", np.stack([harmonic_tone(f, n, p["sr"]) for f in (70.0, 390.0)]), (70.0, 390.0), lens=(n, 4100), **p)
+    p = PARAM_SETS["sr48k"]
+    # 103 Hz (lag 466, m = 7) has 2.2 periods in a frame: tracked within the margins but too coarsely to be held to the true frequency
+    add("sr48k", np.stack([harmonic_tone(f, n, p["sr"]) for f in (110.0, 1000.0, 103.0)]), (110.0, 1000.0, None), lens=(n, 5000, n), **p)
+    add("f0min50", np.stack([harmonic_tone(f, n) for f in (55.0, 62.0)]), (55.0, 62.0), **PARAM_SETS["f0min50"])     # lags 401 (m = 6), 356 (m = 5)
+    add("silence_default", _silence_input(), [None, None])
+    add("silence_low", _silence_input(), [None, None], silence_threshold=SILENCE_LOW)
+    add("voicing_default", _voicing_input()[None], [None])
+    add("voicing_low", _voicing_input()[None], [None], voicing_threshold=VOICING_LOW)
+    return c
+
+
+def case_length(case, b):
+    n = case["wav"].shape[1]
+    return n if case["lens"] is None else int(min(max(case["lens"][b], 0), n))
+
+
+# ---- target-chain inputs at the size edges of f0_targets_kernel: M = 2^ceil(log2 n) and CH = ceil(n / 256) per utterance ------------
+CHAIN_EDGE_FRAMES = ((2, 3, 255, 256, 257, 512, 513), (2048, 2049))
+CHAIN_LONG_N = 4096
+
+
+def _contour(rng, n):
+    t = np.arange(n)
+    f = 170.0 + 50.0 * np.sin(t / 9.0) + 20.0 * np.cos(t / 2.3) + 2.0 * rng.standard_normal(n)
+    f[(t % 23) < 5] = 0
+    return f
+
+
+def gpu_chain_edge_batches():
+    """[(f0 float32 [B, F], frames)] for CHAIN_EDGE_FRAMES, F = the longest of each batch, garbage past each length"""
+    rng = np.random.default_rng(17)
+    out = []
+    for frames in CHAIN_EDGE_FRAMES:
+        F = max(frames)
+        f0 = 100.0 + 200.0 * rng.random((len(frames), F))
+        for b, n in enumerate(frames):
+            f0[b, :n] = _contour(rng, n)
+            if n == 2:
+                f0[b, :2] = (150.5, 212.25)
+            elif n == 3:
+                f0[b, :3] = (180.0, 0.0, 210.5)
+            else:
+                f0[b, 40:70] = 0                                  # a gap across many chunks' summaries at CH = 1
+                f0[b, n - 1] = 0 if b % 2 else 155.5              # the last frame of the utterance: unvoiced / voiced
+        out.append((f0.astype(np.float32), frames))
+    return out
+
+
+def gpu_chain_long_runs():
+    """f0 float32 [5, 4096], every utterance 4096 frames (CH = 16): a leading unvoiced run of 700 frames, an interior gap of 1500, a
+    trailing run of 600, exactly two voiced frames (the first and the last), exactly one voiced frame"""
+    n = CHAIN_LONG_N
+    rng = np.random.default_rng(29)
+    f0 = np.stack([_contour(rng, n) for _ in range(5)])
+    f0[0, :700] = 0
+    f0[1, 1000:2500] = 0
+    f0[2, n - 600:] = 0
+    f0[3] = 0; f0[3, 0] = 150.0; f0[3, n - 1] = 230.0
+    f0[4] = 0; f0[4, 2000] = 175.0
+    f0[0, 700] = 201.5; f0[1, 999] = 140.25; f0[1, 2500] = 260.5; f0[2, n - 601] = 188.0     # the runs' ends are voiced
+    return f0.astype(np.float32), (n,) * 5
 
 
 CHAIN_F, CHAIN_FRAMES = 64, (64, 37, 5, 1)

@@ -4,7 +4,9 @@ against the float64 restatements of tests/pitch_restate.py.
 Tolerance rule (no figure here comes from the kernels): an output's largest error against float64 may be 3 x the largest error of the
 float32 twin - the same restatement run on float32 arrays - on the same input; for f0 the error is relative and has a floor of 1e-5.
 tests/test_pitch_restate_cpu.py::test_decision_margin shows that float32 arithmetic cannot flip a voicing or winner decision on these
-inputs, so every frame is compared and voiced / unvoiced must agree on every frame.  Measured pairs are printed under -s."""
+inputs, so every frame is compared and voiced / unvoiced must agree on every frame.  Measured pairs are printed under -s.
+On the stationary tones the device's f0 is also held to the TRUE frequency, within 2 x the float64 restatement's worst error
+(R.TRACKER_TONES_WORST_REL_ERR, measured on the CPU)."""
 import os
 import sys
 
@@ -37,18 +39,18 @@ def _np(t):
     return t.detach().cpu().numpy()
 
 
-def _check_tracker(name, f0, st, wav, lens):
-    f64, s64 = R.track_pitch(wav, lens)
-    f32, s32 = R.track_pitch(wav, lens, dtype=np.float32)
+def _check_tracker(name, f0, st, wav, lens, ref=None, expect_voiced=True, **params):
+    """ref: (f0_64, strength_64, f0_32, strength_32) of the restatement where a fixture has computed them already"""
+    f64, s64, f32, s32 = ref if ref is not None else R.track_pitch(wav, lens, **params) + R.track_pitch(wav, lens, dtype=np.float32, **params)
     f0, st = _np(f0), _np(st)
     assert f0.dtype == np.float32 and f0.shape == f64.shape and st.shape == s64.shape
     assert np.isfinite(f0).all() and np.isfinite(st).all()
     assert np.array_equal(f0 > 0, f64 > 0), f"{name}: voiced / unvoiced differs at {np.argwhere((f0 > 0) != (f64 > 0))}"
     assert np.array_equal(f32 > 0, f64 > 0)
     v = f64 > 0
-    assert v.any()
-    twin_f = (np.abs(f32.astype(np.float64) - f64)[v] / f64[v]).max()
-    got_f = (np.abs(f0.astype(np.float64) - f64)[v] / f64[v]).max()
+    assert v.any() == expect_voiced
+    twin_f = (np.abs(f32.astype(np.float64) - f64)[v] / f64[v]).max() if v.any() else 0.0
+    got_f = (np.abs(f0.astype(np.float64) - f64)[v] / f64[v]).max() if v.any() else 0.0
     twin_s = np.abs(s32.astype(np.float64) - s64).max()
     got_s = np.abs(st.astype(np.float64) - s64).max()
     print(f"{name}: f0 rel err {got_f:.3e} (twin {twin_f:.3e}), strength abs err {got_s:.3e} (twin {twin_s:.3e}), voiced {v.sum()} / {v.size}")
@@ -218,3 +220,216 @@ def test_pitch_targets_feed_the_model():
     torch.cuda.synchronize()
     assert torch.isfinite(out[0]).all() and torch.isfinite(out[1]).all()
     assert out[0].shape[:2] == (3, Tm)
+
+
+# ------------------------------------------------------------------------------------------------------------------ lag range, rates, thresholds
+# The cases of R.gpu_tracker_cases(): tests/test_pitch_restate_cpu.py holds each of them to the decision margins (test_decision_margin)
+# and shows what each is for (test_cases_reach_the_lag_range_they_claim, test_threshold_cases, test_ragged_case_lengths).
+@pytest.fixture(scope="module")
+def cases():
+    """R.gpu_tracker_cases() with `ref` = (f0_64, strength_64, f0_32, strength_32) of the restatement, computed once"""
+    out = R.gpu_tracker_cases()
+    for c in out.values():
+        c["ref"] = R.track_pitch(c["wav"], c["lens"], **c["params"]) + R.track_pitch(c["wav"], c["lens"], dtype=np.float32, **c["params"])
+    return out
+
+
+def _run_case(c):
+    return PF.track_pitch(_dev(c["wav"]), None if c["lens"] is None else _i32(c["lens"]), **c["params"])
+
+
+@pytest.mark.parametrize("name", ["ground_truth", "edges", "ragged", "ragged_sr16k", "sr16k", "sr48k", "f0min50"])
+def test_tracker_cases_against_float64(cases, name):
+    c = cases[name]
+    wav, lens, hop = c["wav"], c["lens"], c["params"].get("hop", R.HOP)
+    B, N = wav.shape
+    f0, st = _run_case(c)
+    assert f0.shape == (B, 1 + N // hop) and st.shape == f0.shape
+    f64 = _check_tracker(name, f0, st, wav, lens, ref=c["ref"], **c["params"])
+    f0n, stn = _np(f0), _np(st)
+    for b in range(B):
+        n = R.case_length(c, b)
+        fb = 1 + n // hop
+        assert not f0n[b, fb:].any() and not stn[b, fb:].any(), "frames beyond 1 + len // hop must be exactly 0"
+        if c["truth"][b] is not None:                                     # a stationary tone: the device against the TRUE frequency
+            sel, hz = R.full_window_frames(n, hop), c["truth"][b]
+            rel = (np.abs(f0n[b, sel].astype(np.float64) - hz) / hz).max()
+            rel64 = (np.abs(f64[b, sel] - hz) / hz).max()
+            print(f"{name}[{b}] {hz:g} Hz: f0 rel err to the true frequency {rel:.3e} (float64 restatement {rel64:.3e}) over {len(sel)} frames")
+            assert (f0n[b, sel] > 0).all() and rel <= 2.0 * R.TRACKER_TONES_WORST_REL_ERR
+    # each utterance equals its own B = 1 call, bit for bit (other workgroup, other wave, other position among the wave's four frames)
+    w = _dev(wav)
+    for b in range(B):
+        f1, s1 = PF.track_pitch(w[b:b + 1].contiguous(), None if lens is None else _i32([lens[b]]), **c["params"])
+        assert torch.equal(f1[0], f0[b]) and torch.equal(s1[0], st[b]), b
+
+
+def test_octave_cost_decides_on_device(cases):
+    """440 Hz (lags 50, 100, 150) and 700 Hz (31.5, 63, 94.5, ...): the sub-multiples are candidates of almost the fundamental's height in
+    other registers and lanes of the wave; the restatement without the octave cost falls to one at 700 Hz (and the CPU test shows the
+    heights are within 0.0025), so a device argmax that kept the fundamental did so by the cost"""
+    c = cases["ground_truth"]
+    f0 = _np(_run_case(c)[0])
+    sel = R.full_window_frames(R.GROUND_TRUTH_N)
+    plain, _ = R.track_pitch(c["wav"][4:5], use_octave_cost=False)
+    assert (np.abs(plain[0, sel] - 700.0) / 700.0 > 0.3).all()
+    for b, hz in ((3, 440.0), (4, 700.0)):
+        rel = np.abs(f0[b, sel].astype(np.float64) - hz) / hz
+        print(f"octave cost {hz:g} Hz: f0 rel err to the true frequency {rel.max():.3e}")
+        assert rel.max() <= 2.0 * R.TRACKER_TONES_WORST_REL_ERR
+    assert not f0[6].any() and not f0[7].any()                            # noise, silence
+
+
+def test_thresholds_on_device(cases):
+    """silence_threshold 0.03 / 0.01 and voicing_threshold 0.6 / 0.4: the decisions change as in the restatement, the strength does not
+    change by a bit, and the silence peak is the utterance's own"""
+    got = {}
+    for name in ("silence_default", "silence_low", "voicing_default", "voicing_low"):
+        c = cases[name]
+        f0, st = _run_case(c)
+        _check_tracker(name, f0, st, c["wav"], c["lens"], ref=c["ref"], expect_voiced=name != "voicing_default", **c["params"])
+        got[name] = (f0, st)
+    assert torch.equal(got["silence_default"][1], got["silence_low"][1]) and torch.equal(got["voicing_default"][1], got["voicing_low"][1])
+    f_def, f_low = _np(got["silence_default"][0]), _np(got["silence_low"][0])
+    quiet = [t for t in range(f_def.shape[1]) if t * R.HOP - R.FRAME // 2 >= R.SILENCE_STEP]
+    assert len(quiet) >= 10 and not f_def[0, quiet].any() and (f_low[0, quiet] > 0).all()
+    assert (f_def[1] > 0).all() and (f_low[1] > 0).all(), "utterance 1 is above 0.03 x its own peak, below 0.03 x utterance 0's"
+    sel = R.full_window_frames(R.GROUND_TRUTH_N)
+    assert not _np(got["voicing_default"][0]).any() and (_np(got["voicing_low"][0])[0, sel] > 0).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------ target chain at its size edges
+def _check_norm_interp(name, f0, frames):
+    y, uv = K.norm_interp_f0(_dev(f0), _i32(frames))
+    y64, uv64 = R.norm_interp_f0_batch(f0, frames)
+    y32, _ = R.norm_interp_f0_batch(f0, frames, dtype=np.float32)
+    assert np.array_equal(_np(uv), uv64.astype(np.float32))
+    e = np.abs(_np(y).astype(np.float64) - y64).max()
+    twin = np.abs(y32.astype(np.float64) - y64).max()
+    print(f"{name} norm_interp_f0: abs err {e:.3e} (twin {twin:.3e})")
+    assert np.isfinite(_np(y)).all() and e <= TWIN_X * twin
+    for b, n in enumerate(frames):
+        assert not _np(y)[b, n:].any() and not _np(uv)[b, n:].any(), "frames beyond the length must be exactly 0"
+    return y, uv
+
+
+def _check_batch_independence(f0, frames, t, y, uv):
+    """each utterance against its own B = 1 call at its own length: M = 2^ceil(log2 n) and CH = ceil(n / 256) are per utterance"""
+    d = _dev(f0)
+    for b, n in enumerate(frames):
+        row = d[b:b + 1, :n].contiguous()
+        t1 = PF.f0_targets(row, _i32([n]))
+        for key in ("uv", "cont_lf0", "cwt_spec"):
+            assert torch.equal(t1[key][0], t[key][b, :n]), (b, key)
+        for key in ("f0_mean", "f0_std", "valid"):
+            assert torch.equal(t1[key][0], t[key][b]), (b, key)
+        y1, uv1 = K.norm_interp_f0(row, _i32([n]))
+        assert torch.equal(y1[0], y[b, :n]) and torch.equal(uv1[0], uv[b, :n]), b
+
+
+def test_chain_size_edges():
+    """n = 2, 3 (M = 2, 4), 255 / 256 / 257 (the step from CH = 1 to 2, and from M = 256 to 512), 512 / 513, 2048 / 2049"""
+    for f0, frames in R.gpu_chain_edge_batches():
+        name = f"edges F={f0.shape[1]}"
+        t = _check_chain(name, f0, frames)
+        assert _np(t["valid"]).tolist() == [int(n != 2) for n in frames]  # two frames: pycwt's normalisation is NaN at M = 2
+        y, uv = _check_norm_interp(name, f0, frames)
+        _check_batch_independence(f0, frames, t, y, uv)
+
+
+def test_chain_long_unvoiced_runs():
+    """n = 4096 (16 frames per chunk): the nearest voiced neighbour is carried across up to 255 chunk summaries"""
+    f0, frames = R.gpu_chain_long_runs()
+    t = _check_chain("long runs", f0, frames)
+    assert _np(t["valid"]).tolist() == [1, 1, 1, 1, 0]                    # the last: one voiced frame, a constant contour
+    y, uv = _check_norm_interp("long runs", f0, frames)
+    _check_batch_independence(f0, frames, t, y, uv)
+
+
+# ------------------------------------------------------------------------------------------------------------------ composition, capture
+TARGET_KEYS = ("pitch", "f0", "uv", "cwt_spec", "f0_mean", "f0_std", "valid")
+
+
+def _restated_targets(c, dtype):
+    """the chain pitch_targets_from_wav composes: tracker -> frames = 1 + lens // hop -> f0_targets, norm_interp_f0"""
+    hop = c["params"].get("hop", R.HOP)
+    f0, _ = R.track_pitch(c["wav"], c["lens"], dtype=dtype, **c["params"])
+    frames = [1 + int(n) // hop for n in c["lens"]]
+    t = R.f0_targets(f0, frames, dtype=dtype)
+    y, _ = R.norm_interp_f0_batch(f0, frames, dtype=dtype)
+    return dict(t, pitch=f0, f0=y), frames
+
+
+@pytest.mark.parametrize("name", ["ragged", "ragged_sr16k"])
+def test_pitch_targets_from_wav_against_float64(cases, name):
+    c = cases[name]
+    p = dict(c["params"])
+    sr, hop = p.pop("sr", R.SR), p.pop("hop", R.HOP)
+    stft = ctts_amd.TacotronSTFT(1024, hop, 1024 if hop == 256 else 800, 80, sr, 0, 8000)
+    assert (stft.sampling_rate, stft.hop) == (sr, hop)
+    got = PF.pitch_targets_from_wav(_dev(c["wav"]), _i32(c["lens"]), stft, **p)
+    r64, frames = _restated_targets(c, np.float64)
+    r32, _ = _restated_targets(c, np.float32)
+    assert got["pitch"].shape == (5, 1 + c["wav"].shape[1] // hop) and got["mel2ph"] is None
+    assert r64["valid"].tolist() == [1, 0, 1, 0, 1] and np.array_equal(r32["valid"], r64["valid"])
+    assert np.array_equal(_np(got["valid"]), r64["valid"]) and got["valid"].dtype == torch.int32
+    assert np.array_equal(_np(got["uv"]), r64["uv"].astype(np.float32)) and np.array_equal(r32["uv"], r64["uv"])
+    v = r64["pitch"] > 0
+    assert np.array_equal(_np(got["pitch"]) > 0, v) and np.array_equal(r32["pitch"] > 0, v)
+    e = (np.abs(_np(got["pitch"]).astype(np.float64) - r64["pitch"])[v] / r64["pitch"][v]).max()
+    twin = (np.abs(r32["pitch"].astype(np.float64) - r64["pitch"])[v] / r64["pitch"][v]).max()
+    print(f"targets {name} pitch: rel err {e:.3e} (twin {twin:.3e})")
+    assert e <= max(TWIN_X * twin, F0_REL_FLOOR)
+    for key in ("f0", "cwt_spec", "f0_mean", "f0_std"):
+        g = _np(got[key])
+        assert g.dtype == np.float32 and g.shape == r64[key].shape and np.isfinite(g).all(), key
+        e = np.abs(g.astype(np.float64) - r64[key]).max()
+        twin = np.abs(r32[key].astype(np.float64) - r64[key]).max()
+        print(f"targets {name} {key}: abs err {e:.3e} (twin {twin:.3e}), max |ref| {np.abs(r64[key]).max():.3g}")
+        assert e <= TWIN_X * twin, key
+    for b, n in enumerate(frames):
+        for key in ("pitch", "f0", "uv", "cwt_spec"):
+            assert not _np(got[key])[b, max(n, 0):].any(), "frames beyond 1 + len // hop must be exactly 0"
+
+
+def test_pitch_targets_are_capturable(cases):
+    """one captured pitch_targets_from_wav on static buffers, replayed on a second batch with other lengths: bit-identical to the eager
+    call on that batch; the workspace cannot be built inside a capture"""
+    stft = ctts_amd.TacotronSTFT(1024, 256, 1024, 80, 22050, 0, 8000)
+    first = (cases["ragged"]["wav"], (6000, 100, 6144, 0, 3333))
+    second = (np.ascontiguousarray(cases["ground_truth"]["wav"][:5]), (6144, 5000, 2999, 6100, 700))
+    PF.prepare(DEV)
+    wav, lens = _dev(first[0]).clone(), _i32(first[1])
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        PF.pitch_targets_from_wav(wav, lens, stft)
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        captured = PF.pitch_targets_from_wav(wav, lens, stft)
+    for w, n in (first, second, first):
+        wav.copy_(_dev(w))
+        lens.copy_(_i32(n))
+        for key in TARGET_KEYS:
+            captured[key].fill_(7)
+        g.replay()
+        torch.cuda.synchronize()
+        eager = PF.pitch_targets_from_wav(_dev(w), _i32(n), stft)
+        for key in TARGET_KEYS:
+            assert torch.equal(captured[key], eager[key]), key
+        assert (eager["pitch"] > 0).any() and eager["valid"].any()
+    saved = dict(PF._WS)
+    PF._WS.clear()
+    try:
+        g2 = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g2):
+            lens.add_(0)                                                   # the capture is a real one and holds a node
+            with pytest.raises(_lib.CttsError, match="before capturing a graph"):
+                PF.prepare(DEV)
+        assert not PF._WS
+    finally:
+        PF._WS.update(saved)
+    torch.cuda.synchronize()
+    f0, _ = PF.track_pitch(_dev(first[0]), _i32(first[1]))                # the workspace is back and usable
+    assert torch.equal(f0, PF.pitch_targets_from_wav(_dev(first[0]), _i32(first[1]), stft)["pitch"])
