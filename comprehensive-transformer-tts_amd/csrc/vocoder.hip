@@ -1,5 +1,7 @@
 // HiFi-GAN V1 generator (reference hifigan/models.py:112-173) inference kernels, fp32 mode: every Conv1d of the network as ONE launch.
 // The layer geometry (Conv1d / polyphase ConvTranspose1d, lens / len_mul), the epilogue walk and conv_post are vocoder_common.h's.
+// Accepted, V1 or not: B, T, Cin, Cout >= 1; Conv1d with odd k and (k - 1) dil <= 64; ConvTranspose1d with k % u == 0, (k - u) even and
+// k / u <= 65; any input strides and alignment (tests/test_vocoder_contract_gpu.py runs the edges of this contract).
 //
 // vconv_kernel: dilated Conv1d (stride 1, zero padding d (k - 1) / 2) and ConvTranspose1d as an implicit GEMM on the MFMA.
 //   rows = (b, position p), N = output columns, K = taps x Cin.  A workgroup owns 128 positions of one utterance x BN columns.  For every

@@ -1,6 +1,8 @@
 // HiFi-GAN V1 generator, half-precision (fp16) inference mode: the layers of csrc/vocoder.hip with fp16 weights and activations on
 // v_mfma_f32_32x32x16_f16, one MFMA term per product (include/ctts.h, "fp16 mode" - the arithmetic contract lives there).
 // The layer geometry, the epilogue walk and conv_post (vpost_kernel<_Float16>) are vocoder_common.h's.
+// Accepted, V1 or not: B, T, Cin, Cout >= 1; Conv1d with odd k and (k - 1) dil <= 64; ConvTranspose1d with k % u == 0, (k - u) even and
+// k / u <= 65; fp16 or fp32 input of any strides (tests/test_vocoder_contract_gpu.py runs the edges of this contract).
 //
 // vconv_h_kernel: the implicit GEMM of vconv_kernel (rows = positions of one utterance, N = output columns, K = taps x Cin; on-load
 //   leaky_relu; out = fp16(beta * out + alpha * (acc + bias + R))) reshaped for one operand plane:

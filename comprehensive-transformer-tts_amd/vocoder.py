@@ -116,7 +116,9 @@ class ResBlock(nn.Module):
 
 class Generator(nn.Module):
     """models.py:112-173 on the HIP kernels.  Raises NotImplementedError for an upsampler the polyphase kernel does not cover
-    (kernel % rate != 0 or kernel - rate odd) or a dilated conv whose halo exceeds 64 rows."""
+    (kernel % rate != 0 or kernel - rate odd) or a dilated conv whose halo exceeds 64 rows.
+    Accepted: every config with kernel % rate == 0, (kernel - rate) even, kernel / rate <= 65, odd ResBlock kernels with three dilations
+    and (kernel - 1) x dilation <= 64 - V1, V2 and the others tests/test_vocoder_contract_gpu.py runs."""
 
     def __init__(self, h):
         super().__init__()
